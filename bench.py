@@ -17,6 +17,16 @@ GPU (no exec); it fails loudly when fewer than N GPUs are visible.  Rank 0
 prints the JSON line.  `--dry-run` prints the children's environments instead.
 
 Default workload: BASELINE config 3, 1e6 particles per GPU x 500 landmarks.
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(value, ms_per_step, the timed scans' own kernel times and roofline).  `--full`
+adds what takes runs of its own: the CPU baseline (cpu_baseline), the
+workload-robustness runs (extra.robustness) and BASELINE configs 2 and 4
+(extra.configs).  `--dump-outputs DIR` writes what the last timed step computed
+(dump_outputs) as DIR/<name>.npy; the same arguments give the same inputs.
+Every scan grows the maps, which hold 4096 landmarks at most, so more than 500
+timed steps run as windows of 500, each on a fresh handle after its own
+warm-up (run_windows); only the timed scans count.
 """
 from __future__ import annotations
 
@@ -59,13 +69,21 @@ def parse(argv=None):
                     help="dense: the robustness dense-map workload as the timed one (its PMC record)")
     ap.add_argument("--profile-every", type=int, default=PROFILE_EVERY,
                     help="timed scans per scan with kernel events (0: none; the line then lacks kernel times)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run what does not feed it: the CPU baseline, the "
+                         "workload-robustness runs and BASELINE configs 2 and 4 (cpu_baseline, extra.robustness, "
+                         "extra.configs of the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's results (pose estimate, particle state) "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--no-gate-filter", action="store_true",
                     help="A/B: read every visited slot's fp64 data (no fp32 gate mirror)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the workload-robustness runs (60-scan continuation, dense map, no gate filter)")
+                    help="with --full: skip the workload-robustness runs (60-scan continuation, dense map, "
+                         "no gate filter) and configs 2 and 4")
     ap.add_argument("--serial-icp", action="store_true",
                     help="A/B (config 4): align each scan just before its update instead of "
                          "beside the previous scan's update")
@@ -555,6 +573,40 @@ def sharded_local(args, L, n_total, G=2, scans=9, warm=3, page_refs="auto"):
                     "queued before it)"}
 
 
+DUMP_PARTICLES = 262144      # particles whose scalars --dump-outputs keeps (all when fewer)
+DUMP_MAPS = 256              # of those, particles whose whole map it keeps
+DUMP_MAP_BYTES = 32 << 20    # bound of the maps' file (fewer maps when they are long)
+
+
+def dump_outputs(out_dir, f, pose, seed):
+    """--dump-outputs: what the last timed step left a caller, as float64 .npy files:
+    pose [3] (the estimate step() returned) and this rank's particle state as
+    get_state() gives it.  The files stay under 64 MB in all whatever the workload:
+    the scalars (x, y, yaw, w, cnt) of a seeded sample of DUMP_PARTICLES particles,
+    the maps (lm [k][cap][6], zero past each cnt) of DUMP_MAPS of those particles;
+    particle_index / map_index name the sampled particles (a rank's local indices;
+    with several ranks rank 0 writes its shard)."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = f.n_local
+    x, y, yaw, w, cnt, _ = f.get_state(lm_cap=0)
+    rng = np.random.default_rng([seed, 0xD0])
+    idx = np.arange(n) if n <= DUMP_PARTICLES else rng.choice(n, DUMP_PARTICLES, replace=False)
+    cap = max(int(cnt.max()) if n else 0, 1)
+    k = min(len(idx), DUMP_MAPS, max(1, DUMP_MAP_BYTES // (cap * 48)))
+    midx = idx[:k] if n > DUMP_PARTICLES else rng.choice(n, k, replace=False)
+    idx, midx = np.sort(idx), np.sort(midx)
+    lm = np.zeros((k, cap, 6))
+    for j, p in enumerate(midx):
+        c = int(cnt[p])
+        if c:
+            lm[j, :c] = f.get_state(int(p), 1, lm_cap=c)[5][0]
+    arrays = {"pose": np.asarray(pose, dtype=np.float64), "particle_index": idx.astype(np.float64),
+              "x": x[idx], "y": y[idx], "yaw": yaw[idx], "w": w[idx], "cnt": cnt[idx].astype(np.float64),
+              "map_index": midx.astype(np.float64), "lm": lm}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     args = parse(argv)
@@ -602,8 +654,10 @@ def main(argv=None):
             dist.barrier()
         torch.cuda.synchronize()
 
-    R = run_config(args, cfg, n_per_gpu, L, world, rank, dev, comm_id, barrier, args.steps, args.warmup)
+    R = run_windows(args, cfg, n_per_gpu, L, world, rank, dev, comm_id, barrier)
     f, dt, prof, st = R["handle"], R["dt"], R["prof"], R["st"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, f, R["pose"], args.seed)
     N = n_per_gpu * world
     if world > 1:
         tt = torch.tensor([dt], dtype=torch.float64, device=tdev)
@@ -649,7 +703,7 @@ def main(argv=None):
     if rank == 0:
         K = kernel_summary(prof, cfg, n_per_gpu, L)
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cpu = cpu_baseline(L, cfg["P"], args.cpu_seconds, args.seed)
         scan_ms = dt / args.steps * 1e3
         units = f.n_local * args.steps
@@ -706,7 +760,8 @@ def main(argv=None):
                       "resample_shared_slots": sums["copied_slots"],
                       "cow_pages_per_particle_scan": sums["cow"] / units,
                       "pool_collections": st.collections,
-                      "pool_collections_timed": st.collections - R["coll0"],
+                      "pool_collections_timed": R["collections_timed"],
+                      "windows": R["windows"],
                       "pool_pages": st.pool_pages,
                       "pages_opened_per_particle_scan": sums["opened"] / units,
                       "slots_visited_per_particle_scan": sums["visited"] / units,
@@ -716,9 +771,9 @@ def main(argv=None):
         }
         if migration is not None:
             out["extra"]["migration"] = migration
-        extras = not args.no_extras and world == 1
+        extras = args.full and not args.no_extras and world == 1
         if extras and not cfg["icp"]:
-            out["extra"]["robustness"] = robustness(args, f, L, args.warmup + args.steps)
+            out["extra"]["robustness"] = robustness(args, f, L, args.warmup + R["windows"][-1])
         f.close()
         if extras and args.config == "3" and not (args.particles or args.landmarks):
             # the other single-GPU BASELINE configs, each on a fresh handle
@@ -728,6 +783,60 @@ def main(argv=None):
         f.close()
     if world > 1:
         dist.destroy_process_group()
+
+
+MAX_SLOTS = 4096             # landmark slots a map can hold (libfs2 fs2_config max_landmark_capacity)
+WINDOW_MAX = 500             # timed scans on one handle
+
+
+def window_steps(L, warmup):
+    """Timed scans one handle can take.  Every scan of the workload appends its miss
+    (and, once the stream has drifted, some of its hits): at most the 4 measurements
+    of a scan.  A window of `warmup` + this many scans, and the 40 more that --full's
+    long_run_60 adds to the last one, fits a map of L landmarks in MAX_SLOTS even then."""
+    return min(WINDOW_MAX, (MAX_SLOTS - 8 - L) // 4 - warmup - 40)
+
+
+def split_steps(steps, window):
+    """`steps` timed scans as windows of at most `window`."""
+    return [min(window, steps - o) for o in range(0, steps, window)] or [0]
+
+
+def run_windows(args, cfg, n_per_gpu, L, world, rank, dev, comm_id, barrier):
+    """The headline's args.steps timed scans.  A map grows with every scan and holds
+    MAX_SLOTS landmarks at most, so more scans than window_steps() run as windows:
+    each a fresh handle with the same initial state (run_config: populate,
+    args.warmup untimed scans, then its share of the timed ones).  Only the timed
+    scans' wall time is summed; the per-scan sums and the profile's counters add up
+    over the windows, and the last window's handle, pose and stats are returned
+    (its state is what --dump-outputs writes).  Up to window_steps() scans, the
+    default 20 among them, this is one window: one handle, one timed loop."""
+    win = window_steps(L, args.warmup)
+    if win < 1:
+        sys.exit(f"bench.py: --landmarks {L} with --warmup {args.warmup} leaves no room for a timed scan "
+                 f"in a map of {MAX_SLOTS} landmark slots")
+    windows = split_steps(args.steps, win)
+    if world > 1 and len(windows) > 1:
+        sys.exit(f"bench.py: --steps {args.steps} needs {len(windows)} handles in turn; with --gpus > 1 "
+                 f"at most {win} steps run (one handle per rank)")
+    out = None
+    for n in windows:
+        if out is not None:
+            out["handle"].close()
+        R = run_config(args, cfg, n_per_gpu, L, world, rank, dev, comm_id, barrier, n, args.warmup)
+        R["collections_timed"] = R["st"].collections - R["coll0"]
+        if out is not None:
+            R["dt"] += out["dt"]
+            R["collections_timed"] += out["collections_timed"]
+            R["step_ms"] = out["step_ms"] + R["step_ms"]
+            for k, v in out["sums"].items():
+                R["sums"][k] += v
+            for k, v in out["prof"].items():
+                if isinstance(v, (int, float)) and not isinstance(v, bool):
+                    R["prof"][k] += v
+        out = R
+    out["windows"] = windows
+    return out
 
 
 def run_config(args, cfg, n_per_gpu, L, world, rank, dev, comm_id, barrier, steps, warmup):
@@ -839,17 +948,17 @@ def run_config(args, cfg, n_per_gpu, L, world, rank, dev, comm_id, barrier, step
         for s in range(warmup, total_scans):
             f.step_submit(*syn.odometry(s), meas[s])
             if s > warmup:
-                _, st = f.step_wait()
+                pose, st = f.step_wait()
                 step_ms.append(((time.perf_counter() - t1) * 1e3, st.resampled))
                 t1 = time.perf_counter()
                 account(st)
-        _, st = f.step_wait()
+        pose, st = f.step_wait()
         step_ms.append(((time.perf_counter() - t1) * 1e3, st.resampled))
         account(st)
     else:
         for s in range(warmup, total_scans):
             t1 = time.perf_counter()
-            _, st = one_scan(s)
+            pose, st = one_scan(s)
             step_ms.append(((time.perf_counter() - t1) * 1e3, st.resampled))
             account(st)
     barrier()
@@ -870,7 +979,7 @@ def run_config(args, cfg, n_per_gpu, L, world, rank, dev, comm_id, barrier, step
                      "step_submit and step_wait; before_scan: alignment work ahead of a scan's submission"}
             if scans_pts is not None else None)
     return {"handle": f, "dt": dt, "prof": prof, "st": st, "coll0": coll0, "sums": sums, "step_ms": step_ms,
-            "icp_us": icp_us, "icp_host": host, "pipelined": pipelined}
+            "icp_us": icp_us, "icp_host": host, "pipelined": pipelined, "pose": pose}
 
 
 # Algorithmic byte model of the two update kernels (include/fs2.h

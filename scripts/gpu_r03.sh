@@ -20,8 +20,8 @@ if [[ $STAGE == all || $STAGE == tests ]]; then
   tail -1 gpurun_out/smoke.log
 fi
 if [[ $STAGE == all || $STAGE == bench ]]; then
-  timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > gpurun_out/bench.log 2>&1 || { echo bench failed; tail -30 gpurun_out/bench.log; exit 4; }
-  tail -1 gpurun_out/bench.log | cut -c1-1500
+  timeout -k 10 600 python bench.py --full ${BENCH_ARGS:-} > "${BENCH_LOG:=bench.log}" 2>&1 || { echo bench failed; tail -30 "$BENCH_LOG"; exit 4; }
+  tail -1 "$BENCH_LOG" | cut -c1-1500
 fi
 if [[ $STAGE == all || $STAGE == prof ]]; then
   rm -rf /tmp/prof

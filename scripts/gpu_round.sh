@@ -16,8 +16,8 @@ if [[ $STAGE == all || $STAGE == tests ]]; then
   tail -1 gpurun_out/smoke.log
 fi
 if [[ $STAGE == all || $STAGE == bench ]]; then
-  timeout -k 10 600 python bench.py > gpurun_out/bench.log 2>&1 || { echo bench failed; tail -30 gpurun_out/bench.log; exit 4; }
-  tail -1 gpurun_out/bench.log
+  timeout -k 10 600 python bench.py --full > "${BENCH_LOG:=bench.log}" 2>&1 || { echo bench failed; tail -30 "$BENCH_LOG"; exit 4; }
+  tail -1 "$BENCH_LOG"
 fi
 if [[ $STAGE == all || $STAGE == prof ]]; then
   timeout -k 10 600 rocprofv3 --kernel-trace --stats -d /tmp/prof -o run -- python bench.py --no-cpu-baseline --no-extras > gpurun_out/prof.log 2>&1 || { echo prof failed; tail -30 gpurun_out/prof.log; exit 5; }

@@ -1,7 +1,7 @@
 #!/bin/bash
 # GPU session stages, comma-separated (default all = tests,bench,prof):
 #   tests  pytest -m gpu ($TESTS) + smoke
-#   bench  the default bench line (config 3, extra.configs cfg2 / cfg4)
+#   bench  the full bench line (bench.py --full: config 3, extra.configs cfg2 / cfg4) into $BENCH_LOG
 #   prof   rocprofv3 kernel stats of the config-3 bench
 #   host   scripts/host_turnaround.py (host share of a scan)
 #   pmc    HBM bytes by PMC: config 3 and its dense-map variant
@@ -32,8 +32,8 @@ if has host; then
   cut -c1-600 gpurun_out/host_turnaround.json
 fi
 if has bench; then
-  timeout -k 10 600 python bench.py > gpurun_out/bench.log 2>&1 || { echo bench failed; tail -30 gpurun_out/bench.log; exit 4; }
-  tail -1 gpurun_out/bench.log | cut -c1-400
+  timeout -k 10 600 python bench.py --full > "${BENCH_LOG:=bench.log}" 2>&1 || { echo bench failed; tail -30 "$BENCH_LOG"; exit 4; }
+  tail -1 "$BENCH_LOG" | cut -c1-400
 fi
 if has prof; then
   timeout -k 10 600 rocprofv3 --kernel-trace --stats -d /tmp/prof -o run -- python bench.py --no-cpu-baseline --no-extras > gpurun_out/prof.log 2>&1 || { echo prof failed; tail -30 gpurun_out/prof.log; exit 5; }

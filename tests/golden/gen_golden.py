@@ -36,6 +36,8 @@ spec = importlib.util.spec_from_file_location(
 syn = importlib.util.module_from_spec(spec)
 sys.modules["fs2_synthetic"] = syn
 spec.loader.exec_module(syn)
+sys.path.insert(0, os.path.join(REPO, "tests"))
+import golden_io  # noqa: E402  (the sequences' file layout, shared with the tests)
 
 
 def import_reference():
@@ -224,7 +226,7 @@ def run_sequence(name, N, init, scans, seed, cap, gate=8, noises=None, timeout=1
                             (noises or {}).get("meas_noise", 1e-3)]),
         versions=np.array(repr(VERSIONS)),
     )
-    np.savez_compressed(os.path.join(HERE, f"seq_{name}.npz"), **out)
+    golden_io.save_seq(name, out)
     nres = int(np.sum(~np.isnan(uniforms[:S_done])))
     print(f"[{name}] N={N} scans={S_done} resamples={nres} maxcnt={int(st[-1][4].max())}")
     return out

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Run the reference's hot-path primitives on a batch of inputs (test helper).
 
-Used by tests/test_oracle_vs_reference.py, in a subprocess of its own because the
+Used by tests/golden/gen_ref_primitives.py, which records the fixtures of
+tests/test_oracle_vs_reference.py, in a subprocess of its own because the
 reference package is also called `fast_slam_2`.  Imports the reference from
 /root/reference with empty HAL / cv2 stub modules, reads the
 cases from an .npz and writes the reference's outputs to another .npz.  Only the

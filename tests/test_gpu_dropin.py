@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from golden_io import load_seq
 
 pytestmark = pytest.mark.gpu
 
@@ -36,7 +37,7 @@ def fs():
 def test_iterate_numpy_rng_replays_reference(fs, name, rng):
     """rng="numpy" draws numpy's stream on the GPU (fs2_mt_draw), "numpy-host" with numpy."""
     from gpu_util import close, configure
-    d = np.load(os.path.join(GOLDEN, f"seq_{name}.npz"))
+    d = load_seq(name)
     tr, rot, mn = d["noise_cfg"]
     configure(tr, rot, mn, float(d["gate"]))
     N, cap = int(d["N"]), int(d["cap"])

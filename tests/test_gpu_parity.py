@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from golden_io import load_seq
 
 pytestmark = pytest.mark.gpu
 
@@ -139,7 +140,7 @@ def test_icp_submit_wait(fs):
 @pytest.mark.parametrize("name", SEQS)
 def test_sequence_golden(fs, name):
     from gpu_util import close, from_fixture
-    d = load(f"seq_{name}.npz")
+    d = load_seq(name)
     f = from_fixture(d)
     S, cap = int(d["S"]), int(d["cap"])
     for s in range(S):

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from golden_io import load_seq
 from oracle import oracle as orc
 
 SEQS = sorted(f[4:-4] for f in os.listdir(GOLDEN) if f.startswith("seq_") and f.endswith(".npz"))
@@ -118,7 +119,7 @@ def test_icp_golden():
 
 @pytest.mark.parametrize("name", SEQS)
 def test_sequence_golden(name):
-    d = load(f"seq_{name}.npz")
+    d = load_seq(name)
     N, S, cap = int(d["N"]), int(d["S"]), int(d["cap"])
     tr, rot, mn = d["noise_cfg"]
     f = orc.OracleFilter(N, cap, tr_noise=tr, rot_noise=rot, meas_noise=np.eye(2) * mn,

@@ -56,6 +56,8 @@ class ICP:
         """B independent alignments: sources/targets [B][P][2] -> R [B][2][2], t [B][2], iters [B]."""
         src = nat.f64(sources)
         tgt = nat.f64(targets)
+        if src.ndim != 3 or src.shape[2] != 2 or tgt.shape != src.shape:
+            raise ValueError(f"sources {src.shape} and targets {tgt.shape} must both be [B][P][2]")
         B, P = src.shape[0], src.shape[1]
         R = np.empty((B, 4))
         t = np.empty((B, 2))
@@ -69,6 +71,11 @@ class ICP:
     def best_fit_transform(source_points, target_points):
         src = nat.f64(source_points, (-1, 2))
         tgt = nat.f64(target_points, (-1, 2))
+        if len(src) != len(tgt):
+            # the point sets are paired row by row (the reference's matrix product
+            # of the centred sets raises here too)
+            raise ValueError(f"shapes (2,{len(src)}) and ({len(tgt)},2) not aligned: "
+                             f"{len(src)} (dim 1) != {len(tgt)} (dim 0)")
         R = np.empty(4)
         t = np.empty(2)
         nat.check(nat.load().fs2_best_fit_transform(ICP.device, nat.dptr(src), nat.dptr(tgt),

@@ -91,5 +91,43 @@ def main(inp, outp):
     np.savez(outp, **out)
 
 
+def main_ragged(inp, outp):
+    """The ragged mode (tests/golden/gen_ref_edges.py): every case has a shape of
+    its own, so the arrays are named per case (`as_lm_7`, `bf_src_7`, `icp_tgt_7`,
+    `lf_pts_7`; `as_obs`, `as_gate`, `lf_sigma` hold one row per case).  A
+    numpy.linalg.LinAlgError of the association is recorded as index -2."""
+    sys.modules.setdefault("HAL", types.ModuleType("HAL"))
+    sys.modules.setdefault("cv2", types.ModuleType("cv2"))
+    sys.path.insert(0, REF)
+    from fast_slam_2 import ICP, Landmark, LandmarkUtils, LineFilter
+    import fast_slam_2.utils.landmark_utils as lu_mod
+
+    d = np.load(inp)
+    out = {}
+    assoc = []
+    for k in range(len(d["as_obs"])):
+        lm = d[f"as_lm_{k}"]
+        lms = [Landmark(float(r[0]), float(r[1]), r[2:6].reshape(2, 2).copy()) for r in lm]
+        lu_mod.MAXIMUM_LANDMARK_DISTANCE = float(d["as_gate"][k])
+        try:
+            _, idx = LandmarkUtils.associate_landmarks(Landmark(*map(float, d["as_obs"][k])), lms)
+            assoc.append(-1 if idx is None else idx)
+        except np.linalg.LinAlgError:
+            assoc.append(-2)
+    out["assoc"] = np.array(assoc, dtype=np.int64)
+    nb = int(d["bf_n"])
+    R, t = zip(*[ICP.best_fit_transform(d[f"bf_src_{k}"], d[f"bf_tgt_{k}"]) for k in range(nb)])
+    out["bf_R"], out["bf_t"] = np.array(R), np.array(t)
+    ni = int(d["icp_n"])
+    R, t = zip(*[ICP.get_transformation(d[f"icp_src_{k}"], d[f"icp_tgt_{k}"]) for k in range(ni)])
+    out["icp_R"], out["icp_t"] = np.array(R), np.array(t)
+    for k, s in enumerate(d["lf_sigma"]):
+        out[f"lf_{k}"] = LineFilter.filter(d[f"lf_pts_{k}"], sigma=float(s))
+    np.savez(outp, **out)
+
+
 if __name__ == "__main__":
-    main(sys.argv[1], sys.argv[2])
+    if sys.argv[1] == "--ragged":
+        main_ragged(sys.argv[2], sys.argv[3])
+    else:
+        main(sys.argv[1], sys.argv[2])

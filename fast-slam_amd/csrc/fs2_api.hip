@@ -28,6 +28,7 @@
 #include "fs2_kernels.hpp"
 #include "fs2_mtrng.hpp"
 #include "fs2_plan.hpp"
+#include "fs2_repr.hpp"
 
 using namespace fs2;
 static_assert(kMaxRanks <= fs2comm::kShmMaxRanks, "shm transport rank table");
@@ -607,6 +608,12 @@ struct fs2_handle {
         const char *name;
     };
     std::vector<Guard> guards;
+    bool guard = false;                    // FS2_GUARD was set at creation
+    // the viewer JSON's particle block (fs2_particles_json): the device text and the
+    // workgroup offsets, grown on demand and kept between calls
+    char *json_text = nullptr;
+    int64_t *json_boff = nullptr;
+    size_t json_text_cap = 0, json_boff_cap = 0;
 
     MapRef map() const {
         return MapRef{pool, pt[cur], std::max<int64_t>(n, 1), rows, rpool, frame, slb, row_boxes(cur),
@@ -1751,6 +1758,7 @@ static void free_handle(fs2_handle *h) {
     hipFree(h->wpart); hipFree(h->cpart); hipFree(h->part_sq); hipFree(h->part_best_w); hipFree(h->part_best_i); hipFree(h->part_slots);
     hipFree(h->part_maxcnt); hipFree(h->cbuf); hipFree(h->bsum);
     hipFree(h->stats_dev); hipFree(h->noise_dev); hipFree(h->u0_dev); hipFree(h->assoc_dev);
+    hipFree(h->json_text); hipFree(h->json_boff);
     if (h->post_host) hipHostFree(h->post_host);
     hipFree(h->plan);
     if (h->pub_stats) hipHostFree(h->pub_stats);
@@ -1839,6 +1847,7 @@ int fs2_create(const fs2_config *cfg, fs2_handle **out) {
         const char *e = std::getenv("FS2_GUARD");
         return e && *e && std::strcmp(e, "0") != 0;
     }();
+    h->guard = guard;
     auto alloc = [&](void **p, size_t bytes, const char *name) {
         const size_t b = bytes > 0 ? bytes : 16, tot = guard ? b + kGuardBytes : b;
         hipError_t e = hipMalloc(p, tot);
@@ -4215,6 +4224,235 @@ int fs2_plan_sends(const int32_t *mlo, const int32_t *mhi, const int32_t *cnt, i
         run[2 * p + 1] = i1;
         K[p] = E[i1] - E[i0];
         S[p] = C[i1] - C[i0];
+    }
+    return FS2_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------- viewer JSON (fs2_json.hip) ---
+// The particle block of the viewer's JSON from device-resident poses: sizes and
+// offsets (launch_json_sizes), the exact byte count back to the host, then the
+// text (launch_json_write) and one copy straight into the caller's buffer.
+
+namespace {
+
+// Where an emission keeps its device buffers (a handle's, or the per-device cache
+// of the stateless entry point), and how they grow.
+struct JsonBufs {
+    char **text;
+    size_t *text_cap;
+    int64_t **boff;
+    size_t *boff_cap;
+    std::function<hipError_t(void **, size_t *, size_t, const char *)> grow;
+};
+
+// fs2_debug_json_times: device times of the last emission, when enabled
+std::atomic<int> g_json_timing{0};
+std::mutex g_json_ms_mu;
+double g_json_ms[4] = {};
+
+int json_emit(std::string *err, int device, JsonBufs &b, const double *dx, const double *dy, const double *dyaw,
+              int64_t n, int depth, char *buf, int64_t capacity, int64_t *size, hipStream_t s) {
+#define JHIP(expr)                                                                                        \
+    do {                                                                                                  \
+        hipError_t e_ = (expr);                                                                           \
+        if (e_ != hipSuccess) {                                                                           \
+            for (auto &ev_ : ev)                                                                          \
+                if (ev_) (void)hipEventDestroy(ev_);                                                      \
+            return set_err(err, e_ == hipErrorOutOfMemory ? FS2_ERR_OOM : FS2_ERR_HIP, "%s failed: %s", #expr, \
+                           hipGetErrorString(e_));                                                        \
+        }                                                                                                 \
+    } while (0)
+    hipEvent_t ev[5] = {};
+    const bool timed = g_json_timing.load() != 0;
+    const uint64_t *tab = nullptr;
+    JHIP(json_device_table(device, &tab));
+    const int64_t nb = (n + kJsonBlock - 1) / kJsonBlock;
+    JHIP(b.grow((void **)b.boff, b.boff_cap, sizeof(int64_t) * (size_t)(nb + 1), "json_boff"));
+    if (timed)
+        for (auto &e : ev) JHIP(hipEventCreate(&e));
+    if (timed) JHIP(hipEventRecord(ev[0], s));
+    JHIP(launch_json_sizes(tab, dx, dy, dyaw, n, depth, *b.boff, s, ev[1]));
+    if (timed) JHIP(hipEventRecord(ev[2], s));
+    int64_t total = 0;
+    JHIP(hipMemcpyAsync(&total, *b.boff + nb, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    JHIP(hipStreamSynchronize(s));
+    *size = total;
+    double ms[4] = {};
+    int rc = FS2_OK;
+    if (buf && capacity < total) {
+        rc = set_err(err, FS2_ERR_ARG, "the text needs %lld bytes, the buffer holds %lld", (long long)total,
+                     (long long)capacity);
+    } else if (buf) {
+        JHIP(b.grow((void **)b.text, b.text_cap, (size_t)total, "json_text"));
+        JHIP(launch_json_write(tab, dx, dy, dyaw, n, depth, *b.boff, *b.text, s));
+        if (timed) JHIP(hipEventRecord(ev[3], s));
+        JHIP(hipMemcpyAsync(buf, *b.text, (size_t)total, hipMemcpyDeviceToHost, s));
+        if (timed) JHIP(hipEventRecord(ev[4], s));
+        JHIP(hipStreamSynchronize(s));
+    }
+    if (timed) {
+        float t = 0.0f;
+        for (int k = 0; k < (buf && rc == FS2_OK ? 4 : 2); ++k) {
+            JHIP(hipEventElapsedTime(&t, ev[k], ev[k + 1]));
+            ms[k] = t;
+        }
+        std::lock_guard<std::mutex> lk(g_json_ms_mu);
+        std::memcpy(g_json_ms, ms, sizeof ms);
+        for (auto &e : ev) (void)hipEventDestroy(e);
+    }
+    return rc;
+#undef JHIP
+}
+
+// "[]", or nothing to do for a sizing call; returns true when n == 0 was handled
+bool json_empty(std::string *err, int64_t n, char *buf, int64_t capacity, int64_t *size, int *rc) {
+    if (n != 0) return false;
+    *size = 2;
+    *rc = FS2_OK;
+    if (buf && capacity < 2) *rc = set_err(err, FS2_ERR_ARG, "the text needs 2 bytes, the buffer holds %lld", (long long)capacity);
+    else if (buf) std::memcpy(buf, "[]", 2);
+    return true;
+}
+
+// the stateless entry point's buffers, one set per device (as the ICP slots)
+struct JsonDev {
+    hipStream_t stream = nullptr;
+    double *in = nullptr;
+    char *text = nullptr;
+    int64_t *boff = nullptr;
+    size_t in_cap = 0, text_cap = 0, boff_cap = 0;
+};
+std::mutex g_json_mu;
+JsonDev g_jsondev[64];
+
+hipError_t json_grow_plain(void **p, size_t *cap, size_t need, const char *) {
+    if (need <= *cap) return hipSuccess;
+    (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    const size_t want = al16(need + need / 16);
+    hipError_t e = hipMalloc(p, want);
+    if (e == hipErrorOutOfMemory) {
+        (void)hipGetLastError();
+        e = hipMalloc(p, al16(need));
+        if (e == hipSuccess) *cap = al16(need);
+        return e;
+    }
+    if (e == hipSuccess) *cap = want;
+    return e;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fs2_repr_doubles(int32_t device, const double *v, int64_t n, char *out, uint8_t *len, int32_t on_host) {
+    if (n < 0 || (n > 0 && (!v || !out || !len))) return set_err(nullptr, FS2_ERR_ARG, "fs2_repr_doubles: bad arguments");
+    if (on_host) {
+        const uint64_t *tab = json_host_table();
+        for (int64_t k = 0; k < n; ++k) len[k] = (uint8_t)repr_double(v[k], tab, out + k * kReprMax);
+        return FS2_OK;
+    }
+    if (n == 0) return FS2_OK;
+    std::lock_guard<std::mutex> lk(g_scratch_mu);
+    const size_t bv = al16((size_t)n * 8), bo = al16((size_t)n * kReprMax);
+    Scratch *sc = nullptr;
+    int rc = scratch_get(device, bv + bo + al16((size_t)n), &sc);
+    if (rc) return rc;
+    const uint64_t *tab = nullptr;
+    SHIP(json_device_table(device, &tab));
+    double *dv = (double *)sc->buf;
+    char *dout = sc->buf + bv;
+    uint8_t *dlen = (uint8_t *)(sc->buf + bv + bo);
+    SHIP(hipMemcpyAsync(dv, v, (size_t)n * 8, hipMemcpyHostToDevice, sc->stream));
+    SHIP(launch_repr_doubles(tab, dv, n, dout, dlen, sc->stream));
+    SHIP(hipMemcpyAsync(out, dout, (size_t)n * kReprMax, hipMemcpyDeviceToHost, sc->stream));
+    SHIP(hipMemcpyAsync(len, dlen, (size_t)n, hipMemcpyDeviceToHost, sc->stream));
+    SHIP(hipStreamSynchronize(sc->stream));
+    return FS2_OK;
+}
+
+int fs2_poses_json(int32_t device, const double *x, const double *y, const double *yaw, int64_t n, int32_t depth,
+                   char *buf, int64_t capacity, int64_t *size, int32_t where) {
+    if (!size || n < 0 || n > (int64_t)INT32_MAX || (n > 0 && (!x || !y || !yaw)) || depth < 0 ||
+        depth > kJsonMaxDepth || (where != FS2_HOST && where != FS2_DEVICE) || (buf && capacity < 0))
+        return set_err(nullptr, FS2_ERR_ARG, "fs2_poses_json: bad arguments (depth 0..%d)", kJsonMaxDepth);
+    int rc = FS2_OK;
+    if (json_empty(nullptr, n, buf, capacity, size, &rc)) return rc;
+    if (device < 0 || device >= 64) return set_err(nullptr, FS2_ERR_ARG, "bad device %d", device);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev)
+        return set_err(nullptr, FS2_ERR_HIP, "no HIP device %d (libfs2 has no CPU path)", device);
+    std::lock_guard<std::mutex> lk(g_json_mu);
+    SHIP(hipSetDevice(device));
+    JsonDev &d = g_jsondev[device];
+    if (!d.stream) SHIP(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
+    const double *dx = x, *dy = y, *dyaw = yaw;
+    if (where == FS2_HOST) {
+        const size_t b8 = al16((size_t)n * 8);
+        SHIP(json_grow_plain((void **)&d.in, &d.in_cap, 3 * b8, "json_in"));
+        double *px = d.in, *py = (double *)((char *)d.in + b8), *pw = (double *)((char *)d.in + 2 * b8);
+        SHIP(hipMemcpyAsync(px, x, (size_t)n * 8, hipMemcpyHostToDevice, d.stream));
+        SHIP(hipMemcpyAsync(py, y, (size_t)n * 8, hipMemcpyHostToDevice, d.stream));
+        SHIP(hipMemcpyAsync(pw, yaw, (size_t)n * 8, hipMemcpyHostToDevice, d.stream));
+        dx = px;
+        dy = py;
+        dyaw = pw;
+    }
+    JsonBufs b{&d.text, &d.text_cap, &d.boff, &d.boff_cap, json_grow_plain};
+    return json_emit(nullptr, device, b, dx, dy, dyaw, n, depth, buf, capacity, size, d.stream);
+}
+
+int fs2_particles_json(fs2_handle *h, int64_t first, int64_t count, int32_t depth, char *buf, int64_t capacity,
+                       int64_t *size) {
+    if (!h) return set_err(nullptr, FS2_ERR_ARG, "null handle");
+    if (h->pending.on) return set_err(&h->err, FS2_ERR_STATE, "a submitted scan is pending (fs2_iterate_wait first)");
+    if (first < 0 || count < 0 || first + count > h->n)
+        return set_err(&h->err, FS2_ERR_ARG, "range outside local particles");
+    if (!size || depth < 0 || depth > kJsonMaxDepth || (buf && capacity < 0))
+        return set_err(&h->err, FS2_ERR_ARG, "fs2_particles_json: bad arguments (depth 0..%d)", kJsonMaxDepth);
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    {
+        const int rcm = mt_finish(h);    // (as fs2_get_state)
+        h->mt.armed = false;
+        if (rcm) return rcm;
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    int rc = FS2_OK;
+    if (json_empty(&h->err, count, buf, capacity, size, &rc)) return rc;
+    // the handle's buffers are allocated as fs2_create's: with FS2_GUARD each is
+    // followed by the pattern (and sized exactly, so the pattern starts where the text ends)
+    auto grow = [h](void **p, size_t *cap, size_t need, const char *name) -> hipError_t {
+        if (!h->guard) return json_grow_plain(p, cap, need, name);
+        if (need == *cap && *p) return hipSuccess;
+        for (size_t k = 0; k < h->guards.size(); ++k)
+            if (*p && h->guards[k].at == static_cast<char *>(*p) + *cap) {
+                h->guards.erase(h->guards.begin() + (ptrdiff_t)k);
+                break;
+            }
+        (void)hipFree(*p);
+        *p = nullptr;
+        *cap = 0;
+        hipError_t e = hipMalloc(p, need + kGuardBytes);
+        if (e == hipSuccess) e = hipMemset(static_cast<char *>(*p) + need, kGuardByte, kGuardBytes);
+        if (e != hipSuccess) return e;
+        *cap = need;
+        h->guards.push_back(fs2_handle::Guard{static_cast<char *>(*p) + need, name});
+        return hipSuccess;
+    };
+    JsonBufs b{&h->json_text, &h->json_text_cap, &h->json_boff, &h->json_boff_cap, grow};
+    const int c = h->cur;
+    return json_emit(&h->err, h->cfg.device, b, h->x[c] + first, h->y[c] + first, h->yaw[c] + first, count, depth, buf,
+                     capacity, size, h->stream);
+}
+
+int fs2_debug_json_times(int32_t enable, double ms[4]) {
+    if (enable >= 0) g_json_timing.store(enable ? 1 : 0);
+    if (ms) {
+        std::lock_guard<std::mutex> lk(g_json_ms_mu);
+        std::memcpy(ms, g_json_ms, sizeof g_json_ms);
     }
     return FS2_OK;
 }

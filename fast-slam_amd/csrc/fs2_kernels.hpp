@@ -821,6 +821,23 @@ int mt_poly_words();
 bool mt_jump_host(const uint32_t key[624], uint64_t J, uint32_t out[624]);
 hipError_t launch_mt_debug_log(const double *x, int64_t n, double *out, int32_t *amb, hipStream_t s);
 
+// The viewer JSON's particle block (fs2_json.hip; digits: fs2_repr.hpp).  One
+// workgroup writes kJsonBlock items; the nesting depth is limited by the LDS its
+// segment needs (kJsonBlock x the longest item, under 64 KiB).
+constexpr int kJsonBlock = 256;
+constexpr int kJsonMaxDepth = 6;
+const uint64_t *json_host_table();                                  // the powers-of-five table (built once)
+hipError_t json_device_table(int device, const uint64_t **out);     // its copy on `device` (uploaded once)
+int64_t json_max_bytes(int64_t n, int depth);                       // upper bound on the text of n items
+// boff[ceil(n / kJsonBlock) + 1]: each workgroup's first byte, then the text's size
+hipError_t launch_json_sizes(const uint64_t *tab, const double *x, const double *y, const double *yaw, int64_t n,
+                             int depth, int64_t *boff, hipStream_t s, hipEvent_t after_sizes);
+hipError_t launch_json_write(const uint64_t *tab, const double *x, const double *y, const double *yaw, int64_t n,
+                             int depth, const int64_t *boff, char *text, hipStream_t s);
+// out[n][24] text, len[n] (device buffers; out 8-byte aligned)
+hipError_t launch_repr_doubles(const uint64_t *tab, const double *v, int64_t n, char *out, uint8_t *len,
+                               hipStream_t s);
+
 hipError_t launch_icp(int32_t B, int32_t P, const double *src, const double *tgt,
                       int32_t n_tgt, int32_t max_iter, double thr, double *R, double *t,
                       int32_t *iters, hipStream_t s);

@@ -220,6 +220,12 @@ SIGNATURES = [
                                              C.POINTER(C.c_int64)]),
     ("fs2_frontend", C.c_int, [C.c_int32, C.c_int32, _vp, _vp, C.c_int32, _dp, C.c_int32, C.c_int32,
                                C.POINTER(fs2_frontend_out)]),
+    ("fs2_repr_doubles", C.c_int, [C.c_int32, _vp, C.c_int64, _vp, _vp, C.c_int32]),
+    ("fs2_poses_json", C.c_int, [C.c_int32, _vp, _vp, _vp, C.c_int64, C.c_int32, _vp, C.c_int64,
+                                 C.POINTER(C.c_int64), C.c_int32]),
+    ("fs2_particles_json", C.c_int, [_H, C.c_int64, C.c_int64, C.c_int32, _vp, C.c_int64,
+                                     C.POINTER(C.c_int64)]),
+    ("fs2_debug_json_times", C.c_int, [C.c_int32, _vp]),
     ("fs2_debug_philox", C.c_int, [C.c_int32, C.c_int64, _vp, _vp, _vp]),
     ("fs2_debug_normals", C.c_int, [C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int64, _vp]),
     ("fs2_debug_mt_log", C.c_int, [C.c_int32, _vp, C.c_int64, _vp, _vp, C.c_int32]),

@@ -34,6 +34,15 @@ from ..models.particle import Particle
 _REDUCE = {"auto": nat.FS2_REDUCE_AUTO, "sequential": nat.FS2_REDUCE_SEQUENTIAL,
            "parallel": nat.FS2_REDUCE_PARALLEL, "exact": nat.FS2_REDUCE_EXACT}
 
+# A bytes object of a given size that the library fills in place (poses_json): the
+# C API's own way to build one, without a second copy of a 134 MB text.
+_new_bytes = C.pythonapi.PyBytes_FromStringAndSize
+_new_bytes.restype = C.py_object
+_new_bytes.argtypes = [C.c_char_p, C.c_ssize_t]
+_bytes_addr = C.pythonapi.PyBytes_AsString
+_bytes_addr.restype = C.c_void_p
+_bytes_addr.argtypes = [C.py_object]
+
 
 class FastSLAM2:
     """FastSLAM 2.0 particle filter (reference fast_slam_2.py:15-31)."""
@@ -300,6 +309,25 @@ class FastSLAM2:
         nat.check(self._lib.fs2_get_state(self._h, 0, self.n_local, nat.ptr(x), nat.ptr(y), nat.ptr(yaw),
                                           None, None, None, 0, nat.FS2_HOST), self._h)
         return x, y, yaw
+
+    def poses_json(self, depth: int = 1, head: bytes = b"", tail: bytes = b"") -> bytes:
+        """The JSON list of this rank's {"x", "y", "yaw"} objects exactly as
+        json.dump(..., indent=4) writes it at nesting depth `depth`, formatted on the
+        device from the resident poses (fs2_particles_json): one sizing call, then one
+        that fills a bytes object of that size in place.  head / tail: bytes to put
+        before / after the list in the same object (the Serializer's document around
+        it), so the large text is never copied to be joined."""
+        size = C.c_int64()
+        nat.check(self._lib.fs2_particles_json(self._h, 0, self.n_local, int(depth), None, 0,
+                                               C.byref(size)), self._h)
+        n = size.value
+        out = _new_bytes(None, len(head) + n + len(tail))   # uninitialised, ours alone until returned
+        addr = _bytes_addr(out)
+        C.memmove(addr, head, len(head))
+        nat.check(self._lib.fs2_particles_json(self._h, 0, self.n_local, int(depth),
+                                               addr + len(head), n, C.byref(size)), self._h)
+        C.memmove(addr + len(head) + n, tail, len(tail))
+        return out
 
     def cluster_landmarks(self, eps: float = 0.5, min_fraction: float = 0.7):
         """Centres [K][2] of DBSCAN over every particle's landmarks, on the device

@@ -399,6 +399,45 @@ int fs2_associate(int32_t device, const double observed[2], const double *lm, in
 int fs2_mahalanobis(int32_t device, const double *a, const double *b, const double *cov,
                     int32_t K, double *out);
 
+/* ------------------------------------------------------------ viewer JSON ---- */
+
+/* Replaces the particle part of Serializer.serialize (utils/serializer.py:20-49):
+ * json.dump(..., indent=4) formats every pose coordinate with float.__repr__ in the
+ * interpreter; here the text is written on the device, byte for byte.
+ *
+ * fs2_repr_doubles: json.dumps(v[k]) for each of n doubles -- float.__repr__ for
+ * finite values (the shortest digits that read back, the closest such string, ties
+ * to the even digit; d[.ddd]e+XX / e-XX when the first digit's decimal exponent is < -4
+ * or >= 16, else positional with ".0" where no '.' would appear), NaN for every
+ * NaN, Infinity / -Infinity.  out[n][24] text (unused tail bytes undefined), len[n]
+ * lengths; host buffers.  on_host = 1 runs the same code on the CPU (tests; needs
+ * no device). */
+int fs2_repr_doubles(int32_t device, const double *v, int64_t n, char *out, uint8_t *len,
+                     int32_t on_host);
+
+/* Text of the JSON list of {"x","y","yaw"} objects exactly as json.dump(..., indent=4)
+ * writes it at nesting depth `depth` (0..6; "[]" for n = 0; serializer.py:39 of the
+ * reference).  x, y, yaw: n values each, where = FS2_HOST / FS2_DEVICE.  buf: host,
+ * `capacity` bytes, may be NULL.  *size always receives the exact byte count (no
+ * terminator).  buf == NULL returns FS2_OK after sizing; capacity < *size fails with
+ * FS2_ERR_ARG and writes nothing. */
+int fs2_poses_json(int32_t device, const double *x, const double *y, const double *yaw,
+                   int64_t n, int32_t depth, char *buf, int64_t capacity, int64_t *size,
+                   int32_t where);
+
+/* The same for local particles [first, first + count) of a handle, from its device-resident
+ * poses (the current buffer set).  Preconditions and errors as fs2_get_state: FS2_ERR_STATE
+ * while scans are outstanding; ends a pending deferred draw; synchronises the handle's
+ * stream.  A sharded handle reports its own shard. */
+int fs2_particles_json(fs2_handle *h, int64_t first, int64_t count, int32_t depth, char *buf,
+                       int64_t capacity, int64_t *size);
+
+/* Measurement hook (scripts/json_probe.py): enable = 1 / 0 turns HIP-event timing of
+ * the two entry points above on / off (process-wide; -1 leaves it); ms (nullable)
+ * receives the last timed emission's device times: the size pass, the offset scan,
+ * the write pass, the download (the last two 0 for a sizing call). */
+int fs2_debug_json_times(int32_t enable, double ms[4]);
+
 /* Test hooks of the device generator that replaces the reference's
  * np.random draws when rng="device" (fast_slam_2.py:79,81 motion noise, :183
  * resample start): Philox4x32-10 (Salmon et al., Random123) and the motion

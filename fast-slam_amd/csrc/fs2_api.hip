@@ -351,6 +351,51 @@ static void gm_free(GrowMem &g) {
     g = GrowMem{};
 }
 
+// One of a handle's two pools (fs2_kernels.hpp): the landmark pages, or the slot
+// records.  `n` items at `data`, a collection mark per item, and the free list:
+// ids [cursor, nfree) are free, [0, cursor) reserved since the last collection.
+// grow(), reserve() and the collections below work on either.
+struct Pool {
+    const char *name;                      // in messages: "page" / "record"
+    size_t item_bytes;                     // kPageBytes / kRecBytes
+    int64_t id_limit;                      // the largest pool its ids can name: kIdMask / kRecIdLimit
+    char *data = nullptr;
+    int64_t n = 0;                         // items in the pool
+    GrowMem vm;                            // in-place growth of the data (base null: hipMalloc)
+    uint8_t *mark = nullptr;               // collection marks, one byte per item
+    GrowMem mark_vm;                       // (marks and free list grow in place alike)
+    uint32_t *freel = nullptr;             // free ids [0, nfree)
+    GrowMem freel_vm;
+    int64_t nfree = 0, cursor = 0;         // free ids listed / reserved since the last collection
+    uint8_t epoch = 0;                     // the last collection's mark value (0: none yet, or marks moved)
+    int64_t *bcnt = nullptr;               // sweep block counts -> offsets
+    int64_t bcnt_cap = 0;                  // of them allocated (collect_blocks)
+    int64_t *nfree_dev = nullptr;          // the sweep's count of free ids
+
+    int64_t room() const { return nfree - cursor; }      // listed free, not yet reserved
+    int64_t live() const { return n - room(); }
+    bool in_place() const { return vm.base && data == vm.base; }
+    // the next collection's epoch (the marks cleared when the byte wraps)
+    hipError_t next_epoch(hipStream_t s) {
+        if (epoch == 255) {
+            const hipError_t e = hipMemsetAsync(mark, 0, (size_t)n, s);
+            if (e != hipSuccess) return e;
+            epoch = 0;
+        }
+        epoch += 1;
+        return hipSuccess;
+    }
+    bool mapped() const { return vm.base || mark_vm.base || freel_vm.base; }
+    // (fs2_destroy, the device drained around it when anything is mapped())
+    void release() {
+        if (vm.base) gm_free(vm); else hipFree(data);
+        if (mark_vm.base) gm_free(mark_vm); else hipFree(mark);
+        if (freel_vm.base) gm_free(freel_vm); else hipFree(freel);
+        hipFree(bcnt);
+        hipFree(nfree_dev);
+    }
+};
+
 }  // namespace
 
 // One draw's context, from its start (mt_begin) to its end (mt_end): a
@@ -376,12 +421,10 @@ struct fs2_handle {
     int cur = 0;
     double *x[2] = {}, *y[2] = {}, *yaw[2] = {}, *w[2] = {};
     int32_t *cnt[2] = {};
-    // landmark pages (fs2_kernels.hpp): pool, page tables A/B, free list
-    char *pool = nullptr;
-    int64_t npool = 0;                     // pages in the pool
-    GrowMem pool_vm, rpool_vm;             // in-place growth of the page / record pools (base null: hipMalloc)
-    GrowMem mark_vm, freel_vm, rmark_vm, rfreel_vm;   // their marks and free lists, alike
-    int64_t bcnt_cap = 0, rbcnt_cap = 0;   // sweep block counts allocated (collect_blocks)
+    // landmark pages and slot records (fs2_kernels.hpp): the pools (the records are
+    // collected with the pages), page tables A/B
+    Pool pages{"page", kPageBytes, (int64_t)kIdMask};
+    Pool records{"record", kRecBytes, (int64_t)kRecIdLimit};
     Desc *pt[2] = {};                      // [rows][n] page descriptors (A/B across resamples)
     uint32_t *bbox[2] = {};                // [nblocks][kBBoxRows] workgroup row boxes of pt[0] / pt[1]
     XDesc *rdesc = nullptr;                // received particles' rows [n_recv][rows] (with boxes)
@@ -399,23 +442,8 @@ struct fs2_handle {
     uint32_t *ext_dev = nullptr;           // device: import extent (float bits)
     size_t rdesc_cap = 0;
     int rows = 0;                          // page-table rows allocated
-    uint32_t *freel = nullptr;             // free page ids [0, nfree)
-    int64_t nfree = 0, cursor = 0;         // free pages listed / reserved since the last collection
-    uint8_t *mark = nullptr;               // collection marks, one byte per page
     uint32_t *sent_mask = nullptr;         // sharded: per page, the ranks it went to since the last collection
-    uint8_t epoch = 0;
-    int64_t *bcnt = nullptr;               // sweep block counts -> offsets
-    int64_t *nfree_dev = nullptr;
     uint64_t collections = 0;
-    // slot records (fs2_kernels.hpp): pool, free list, marks (collected with the pages)
-    char *rpool = nullptr;
-    int64_t nrecs = 0;
-    uint32_t *rfreel = nullptr;
-    int64_t rnfree = 0, rcursor = 0;
-    uint8_t *rmark = nullptr;
-    uint8_t repoch = 0;
-    int64_t *rbcnt = nullptr;
-    int64_t *rnfree_dev = nullptr;
     int64_t u_recv = 0;                    // distinct pages received by the last resample
     int32_t *rank_d = nullptr, *rank_e = nullptr;
     int64_t *iblk = nullptr;
@@ -616,7 +644,7 @@ struct fs2_handle {
     size_t json_text_cap = 0, json_boff_cap = 0;
 
     MapRef map() const {
-        return MapRef{pool, pt[cur], std::max<int64_t>(n, 1), rows, rpool, frame, slb, row_boxes(cur),
+        return MapRef{pages.data, pt[cur], std::max<int64_t>(n, 1), rows, records.data, frame, slb, row_boxes(cur),
                       refs_shared ? peers_dev : nullptr};
     }
     // row boxes of buffer b, while the maps fit them (fs2_kernels.hpp)
@@ -781,8 +809,8 @@ static int refs_short(fs2_handle *h, const char *what) {
 
 // Collect the page pool: every page the current page table does not refer to
 // becomes free (fs2_pages.hip); the reservation cursor restarts.  With
-// `records`, the record pool is collected from the same marks as well.
-static int collect_body(fs2_handle *h, bool records);
+// `recs_too`, the record pool is collected from the same marks as well.
+static int collect_body(fs2_handle *h, bool recs_too);
 // (host wall time of collections and growths, fs2_profile)
 struct PoolTimer {
     fs2_handle *h;
@@ -799,37 +827,38 @@ struct PoolTimer {
         }
     }
 };
-static int collect(fs2_handle *h, bool records) {
+static int collect(fs2_handle *h, bool recs_too) {
     PoolTimer pt{h, false};
-    return collect_body(h, records);
+    return collect_body(h, recs_too);
 }
-static int collect_body(fs2_handle *h, bool records) {
+// The record half of a collection, enqueued after the pages' marks of this epoch
+// are complete: the records of marked pages stay.  Its count is on the host once
+// the caller has drained the stream; the futile-collection bound (reserve) starts over.
+static int collect_records(fs2_handle *h) {
+    Pool &p = h->pages, &r = h->records;
+    if (r.n <= 0) return FS2_OK;
     hipStream_t s = h->stream;
-    if (h->epoch == 255) {
-        HIP_TRY(h, hipMemsetAsync(h->mark, 0, (size_t)h->npool, s));
-        h->epoch = 0;
-    }
-    h->epoch += 1;
-    HIP_TRY(h, launch_collect(h->map(), h->cnt[h->cur], h->npool, h->mark, h->epoch, h->bcnt, h->freel,
-                              h->nfree_dev, s));
-    HIP_TRY(h, hipMemcpyAsync(&h->nfree, h->nfree_dev, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    if (records && h->nrecs > 0) {
-        if (h->repoch == 255) {
-            HIP_TRY(h, hipMemsetAsync(h->rmark, 0, (size_t)h->nrecs, s));
-            h->repoch = 0;
-        }
-        h->repoch += 1;
-        HIP_TRY(h, launch_collect_records(h->pool, h->npool, h->mark, h->epoch, h->nrecs, h->rmark, h->repoch,
-                                          h->rbcnt, h->rfreel, h->rnfree_dev, s));
-        HIP_TRY(h, hipMemcpyAsync(&h->rnfree, h->rnfree_dev, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        h->rcursor = 0;
-        h->appends_since_rcollect = 0;
-        h->rcollect_exact = true;
-    }
+    HIP_TRY(h, r.next_epoch(s));
+    HIP_TRY(h, launch_collect_records(p.data, p.n, p.mark, p.epoch, r.n, r.mark, r.epoch, r.bcnt, r.freel,
+                                      r.nfree_dev, s));
+    HIP_TRY(h, hipMemcpyAsync(&r.nfree, r.nfree_dev, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    r.cursor = 0;
+    h->appends_since_rcollect = 0;
+    h->rcollect_exact = true;
+    return FS2_OK;
+}
+static int collect_body(fs2_handle *h, bool recs_too) {
+    hipStream_t s = h->stream;
+    Pool &p = h->pages;
+    HIP_TRY(h, p.next_epoch(s));
+    HIP_TRY(h, launch_collect(h->map(), h->cnt[h->cur], p.n, p.mark, p.epoch, p.bcnt, p.freel, p.nfree_dev, s));
+    HIP_TRY(h, hipMemcpyAsync(&p.nfree, p.nfree_dev, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    if (recs_too)
+        if (int rc = collect_records(h)) return rc;
     // page ids are recycled from here on: the transfer probe starts over
-    if (h->sent_mask) HIP_TRY(h, hipMemsetAsync(h->sent_mask, 0, sizeof(uint32_t) * (size_t)h->npool, s));
+    if (h->sent_mask) HIP_TRY(h, hipMemsetAsync(h->sent_mask, 0, sizeof(uint32_t) * (size_t)p.n, s));
     HIP_TRY(h, hipStreamSynchronize(s));
-    h->cursor = 0;
+    p.cursor = 0;
     h->collections += 1;
     return FS2_OK;
 }
@@ -865,9 +894,13 @@ static int share_pools(fs2_handle *h, bool first) {
     // the resamples send pages, as they may (no reference has crossed yet).
     bool ok = true;
     std::string why;
+    const struct {
+        void *base;
+        const GrowMem *vm;
+    } shared[3] = {{h->pages.data, &h->pages.vm}, {h->records.data, &h->records.vm}, {h->pages.mark, &h->pages.mark_vm}};
     for (int what = 0; what < 3; ++what) {
-        void *base = what == 0 ? (void *)h->pool : what == 1 ? (void *)h->rpool : (void *)h->mark;
-        const GrowMem &vm = what == 0 ? h->pool_vm : what == 1 ? h->rpool_vm : h->mark_vm;
+        void *base = shared[what].base;
+        const GrowMem &vm = *shared[what].vm;
         CommTimer ct(h);
         std::string e;
         trace(h, "share", what);
@@ -935,48 +968,29 @@ static int share_pools(fs2_handle *h, bool first) {
 // all-gather is the barrier before anyone sweeps.  Records as in collect(): the
 // remote-marked pages mark their records too.
 static int collect_collective(fs2_handle *h) {
-    trace(h, "collect_collective", (int)(h->nfree - h->cursor));
+    Pool &p = h->pages;
+    trace(h, "collect_collective", (int)p.room());
     hipStream_t s = h->stream;
-    const int G = h->cfg.world_size;
-    if (h->epoch == 255) {
-        HIP_TRY(h, hipMemsetAsync(h->mark, 0, (size_t)h->npool, s));
-        h->epoch = 0;
-    }
-    h->epoch += 1;
-    HIP_TRY(h, hipMemsetAsync(h->ep_dev, h->epoch, 1, s));
+    HIP_TRY(h, p.next_epoch(s));
+    HIP_TRY(h, hipMemsetAsync(h->ep_dev, p.epoch, 1, s));
     {
         CommTimer ct(h);
         const int rc = h->tp->allgather(h->ep_dev, h->epochs_dev, 1, s, &h->err);
         if (rc) return rc;
     }
-    HIP_TRY(h, launch_collect_mark(h->map(), h->cnt[h->cur], h->mark, h->epoch, h->epochs_dev, s));
+    HIP_TRY(h, launch_collect_mark(h->map(), h->cnt[h->cur], p.mark, p.epoch, h->epochs_dev, s));
     {
         CommTimer ct(h);
         const int rc = h->tp->allgather(h->ep_dev, h->epochs_dev + kMaxRanks, 1, s, &h->err);
         if (rc) return rc;
     }
-    HIP_TRY(h, launch_collect_sweep(h->npool, h->mark, h->epoch, h->bcnt, h->freel, h->nfree_dev, s));
-    HIP_TRY(h, hipMemcpyAsync(&h->nfree, h->nfree_dev, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    if (h->nrecs > 0) {
-        if (h->repoch == 255) {
-            HIP_TRY(h, hipMemsetAsync(h->rmark, 0, (size_t)h->nrecs, s));
-            h->repoch = 0;
-        }
-        h->repoch += 1;
-        HIP_TRY(h, launch_collect_records(h->pool, h->npool, h->mark, h->epoch, h->nrecs, h->rmark, h->repoch,
-                                          h->rbcnt, h->rfreel, h->rnfree_dev, s));
-        HIP_TRY(h, hipMemcpyAsync(&h->rnfree, h->rnfree_dev, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    }
+    HIP_TRY(h, launch_collect_sweep(p.n, p.mark, p.epoch, p.bcnt, p.freel, p.nfree_dev, s));
+    HIP_TRY(h, hipMemcpyAsync(&p.nfree, p.nfree_dev, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    if (int rc = collect_records(h)) return rc;
     HIP_TRY(h, hipStreamSynchronize(s));
     if (int rc = h->tp->status(&h->err)) return rc;
-    h->cursor = 0;
-    h->rcursor = 0;
-    if (h->nrecs > 0) {            // (as collect_body: the futile-collection bound starts over)
-        h->appends_since_rcollect = 0;
-        h->rcollect_exact = true;
-    }
+    p.cursor = 0;
     h->collections += 1;
-    (void)G;
     return FS2_OK;
 }
 
@@ -1026,8 +1040,7 @@ static int ensure_bcnt(fs2_handle *h, int64_t **b, int64_t *cap, int64_t items) 
 // the all-gathered records), together -- pools shared by IPC cannot grow in place:
 // every rank unmaps the others' pools, a rendezvous, each reallocates its own
 // (page and record ids keep their meaning), and the pools are shared anew.
-static int grow_pool(fs2_handle *h, int64_t pages);
-static int grow_recs(fs2_handle *h, int64_t n);
+static int grow(fs2_handle *h, Pool &p, int64_t items);
 static int regrow_collective(fs2_handle *h, int64_t pages_to, int64_t recs_to) {
     trace(h, "regrow pages_to (M)", (int)(pages_to >> 20));
     trace(h, "regrow recs_to (M)", (int)(recs_to >> 20));
@@ -1043,178 +1056,125 @@ static int regrow_collective(fs2_handle *h, int64_t pages_to, int64_t recs_to) {
     h->refs_shared = false;
     int rc = FS2_OK;
     // (a target of 0: this rank's pool stays; it still takes part)
-    if (pages_to > 0)
-        rc = grow_pool(h, std::min<int64_t>(std::max(h->npool + h->npool / 2, pages_to), (int64_t)kRefIdMask - 1024));
-    if (!rc && recs_to > 0)
-        rc = grow_recs(h, std::min<int64_t>(std::max(h->nrecs + h->nrecs / 2, recs_to), (int64_t)kRecIdLimit));
+    Pool &p = h->pages, &r = h->records;
+    if (pages_to > 0) rc = grow(h, p, std::min<int64_t>(std::max(p.n + p.n / 2, pages_to), (int64_t)kRefIdMask - 1024));
+    if (!rc && recs_to > 0) rc = grow(h, r, std::min<int64_t>(std::max(r.n + r.n / 2, recs_to), r.id_limit));
     if (rc) return rc;
     h->grows += 1;
     return share_pools(h, false);
 }
 
-// Pool of `pages` pages (existing pages keep their ids), its free list and marks.
-// The new pages are free: their ids join the free list after the entries already
+// A pool of `items` items (existing ones keep their ids), its free list and marks.
+// The new items are free: their ids join the free list after the entries already
 // listed (no collection).  In place (GrowMem) when the handle's pools are not
 // shared, else allocate and copy.
-static int grow_pool(fs2_handle *h, int64_t pages) {
-    if (pages <= h->npool) return FS2_OK;
-    if (h->refs_shared) return refs_short(h, "page");
+static int grow(fs2_handle *h, Pool &p, int64_t items) {
+    if (items <= p.n) return FS2_OK;
+    if (h->refs_shared) return refs_short(h, p.name);
     PoolTimer pt{h, true};
-    if (h->refs && pages > (int64_t)kRefIdMask)
+    const bool pages = &p == &h->pages;
+    if (pages && h->refs && items > (int64_t)kRefIdMask)
         return set_err(&h->err, FS2_ERR_CAPACITY, "page_refs mode: %lld pages exceed the %u local page ids",
-                       (long long)pages, kRefIdMask);
-    if (pages > (int64_t)kIdMask)
-        return set_err(&h->err, FS2_ERR_OOM, "page pool of %lld pages exceeds the id space", (long long)pages);
+                       (long long)items, kRefIdMask);
+    if (items > p.id_limit)
+        return set_err(&h->err, FS2_ERR_OOM, "%s pool of %lld %ss exceeds the %sid space", p.name, (long long)items,
+                       p.name, pages ? "" : "32-bit ");
     hipStream_t s = h->stream;
     HIP_TRY(h, hipStreamSynchronize(s));
     // in place (VMM); page_refs between processes: chunks exportable as POSIX
     // descriptors (vm_share), mapped by the peers (Transport::share_vm)
-    if (!h->pool) gm_init(h->pool_vm, h->cfg.device, (size_t)pages * kPageBytes, h->vm_share);
-    if (h->pool_vm.base && gm_grow(h->pool_vm, (size_t)pages * kPageBytes) == hipSuccess) {
-        h->pool = h->pool_vm.base;
+    const size_t bytes = (size_t)items * p.item_bytes;
+    if (!p.data) gm_init(p.vm, h->cfg.device, bytes, h->vm_share);
+    if (p.vm.base && gm_grow(p.vm, bytes) == hipSuccess) {
+        p.data = p.vm.base;
     } else {
         // beyond the reservation, or the mapping failed: allocate and copy (the
         // reserved range is left for good)
-        char *pool = nullptr;
-        HIP_TRY(h, hipMalloc(&pool, (size_t)pages * kPageBytes));
+        char *data = nullptr;
+        HIP_TRY(h, hipMalloc(&data, bytes));
         // (from the mapping itself: a growth that failed after moving it left the
-        // pages at pool_vm.base, not at the h->pool held before)
-        if (h->pool) HIP_TRY(h, copy_sync(h, pool, h->pool_vm.base ? h->pool_vm.base : h->pool,
-                                          (size_t)h->npool * kPageBytes, hipMemcpyDeviceToDevice));
-        if (h->pool_vm.base) {
-            gm_free(h->pool_vm);
+        // items at vm.base, not at the p.data held before)
+        if (p.data) HIP_TRY(h, copy_sync(h, data, p.vm.base ? p.vm.base : p.data, (size_t)p.n * p.item_bytes,
+                                         hipMemcpyDeviceToDevice));
+        if (p.vm.base) {
+            gm_free(p.vm);
             h->vm_fallbacks += 1;
         } else {
-            hipFree(h->pool);
+            hipFree(p.data);
         }
-        h->pool = pool;
+        p.data = data;
     }
     // marks and free list: in place with the pool (new marks zero, new ids after
     // the entries listed so far), else moved
-    const bool vm = h->pool == h->pool_vm.base && h->pool_vm.base != nullptr;
+    const bool vm = p.in_place();
     bool moved = false;
-    int rc = grow_side(h, h->mark_vm, (void **)&h->mark, (size_t)pages, (size_t)h->npool, vm, &moved);
+    int rc = grow_side(h, p.mark_vm, (void **)&p.mark, (size_t)items, (size_t)p.n, vm, &moved);
     if (rc) return rc;
     if (moved) {
-        HIP_TRY(h, hipMemsetAsync(h->mark, 0, (size_t)pages, s));
-        h->epoch = 0;
+        HIP_TRY(h, hipMemsetAsync(p.mark, 0, (size_t)items, s));
+        p.epoch = 0;
     } else {
-        HIP_TRY(h, hipMemsetAsync(h->mark + h->npool, 0, (size_t)(pages - h->npool), s));
+        HIP_TRY(h, hipMemsetAsync(p.mark + p.n, 0, (size_t)(items - p.n), s));
     }
-    rc = grow_side(h, h->freel_vm, (void **)&h->freel, sizeof(uint32_t) * (size_t)pages,
-                   sizeof(uint32_t) * (size_t)std::max<int64_t>(h->nfree, 0), vm, &moved);
+    rc = grow_side(h, p.freel_vm, (void **)&p.freel, sizeof(uint32_t) * (size_t)items,
+                   sizeof(uint32_t) * (size_t)std::max<int64_t>(p.nfree, 0), vm, &moved);
     if (rc) return rc;
-    HIP_TRY(h, launch_iota_from(h->freel + h->nfree, (uint32_t)h->npool, pages - h->npool, s));
-    h->nfree += pages - h->npool;
-    if (h->cfg.world_size > 1) {
+    HIP_TRY(h, launch_iota_from(p.freel + p.nfree, (uint32_t)p.n, items - p.n, s));
+    p.nfree += items - p.n;
+    if (pages && h->cfg.world_size > 1) {       // the transfer probe's mask, one word per page
         hipFree(h->sent_mask);
         h->sent_mask = nullptr;
-        HIP_TRY(h, hipMalloc(&h->sent_mask, sizeof(uint32_t) * (size_t)pages));
-        HIP_TRY(h, hipMemsetAsync(h->sent_mask, 0, sizeof(uint32_t) * (size_t)pages, s));
+        HIP_TRY(h, hipMalloc(&h->sent_mask, sizeof(uint32_t) * (size_t)items));
+        HIP_TRY(h, hipMemsetAsync(h->sent_mask, 0, sizeof(uint32_t) * (size_t)items, s));
     }
-    rc = ensure_bcnt(h, &h->bcnt, &h->bcnt_cap, pages);
+    rc = ensure_bcnt(h, &p.bcnt, &p.bcnt_cap, items);
     if (rc) return rc;
-    h->npool = pages;
+    p.n = items;
     return FS2_OK;
 }
 
-// Record pool of `n` records (existing records keep their ids), free list, marks:
-// like grow_pool.
-static int grow_recs(fs2_handle *h, int64_t n) {
-    if (n <= h->nrecs) return FS2_OK;
-    if (h->refs_shared) return refs_short(h, "record");
-    PoolTimer pt{h, true};
-    if (n > (int64_t)kRecIdLimit)
-        return set_err(&h->err, FS2_ERR_OOM, "record pool of %lld records exceeds the 32-bit id space",
-                       (long long)n);
-    hipStream_t s = h->stream;
-    HIP_TRY(h, hipStreamSynchronize(s));
-    if (!h->rpool) gm_init(h->rpool_vm, h->cfg.device, (size_t)n * kRecBytes, h->vm_share);   // (as grow_pool)
-    if (h->rpool_vm.base && gm_grow(h->rpool_vm, (size_t)n * kRecBytes) == hipSuccess) {
-        h->rpool = h->rpool_vm.base;
-    } else {
-        char *rp = nullptr;
-        HIP_TRY(h, hipMalloc(&rp, (size_t)n * kRecBytes));
-        if (h->rpool) HIP_TRY(h, copy_sync(h, rp, h->rpool_vm.base ? h->rpool_vm.base : h->rpool,
-                                           (size_t)h->nrecs * kRecBytes, hipMemcpyDeviceToDevice));
-        if (h->rpool_vm.base) {
-            gm_free(h->rpool_vm);
-            h->vm_fallbacks += 1;
-        } else {
-            hipFree(h->rpool);
-        }
-        h->rpool = rp;
-    }
-    const bool vm = h->rpool == h->rpool_vm.base && h->rpool_vm.base != nullptr;
-    bool moved = false;
-    int rc = grow_side(h, h->rmark_vm, (void **)&h->rmark, (size_t)n, (size_t)h->nrecs, vm, &moved);
-    if (rc) return rc;
-    if (moved) {
-        HIP_TRY(h, hipMemsetAsync(h->rmark, 0, (size_t)n, s));
-        h->repoch = 0;
-    } else {
-        HIP_TRY(h, hipMemsetAsync(h->rmark + h->nrecs, 0, (size_t)(n - h->nrecs), s));
-    }
-    rc = grow_side(h, h->rfreel_vm, (void **)&h->rfreel, sizeof(uint32_t) * (size_t)n,
-                   sizeof(uint32_t) * (size_t)std::max<int64_t>(h->rnfree, 0), vm, &moved);
-    if (rc) return rc;
-    HIP_TRY(h, launch_iota_from(h->rfreel + h->rnfree, (uint32_t)h->nrecs, n - h->nrecs, s));
-    h->rnfree += n - h->nrecs;
-    rc = ensure_bcnt(h, &h->rbcnt, &h->rbcnt_cap, n);
-    if (rc) return rc;
-    h->nrecs = n;
-    return FS2_OK;
-}
-
-// Reserve `need` free pages (collecting, then growing the pool, when short);
-// returns the reservation's first index into freel.  A launch that needs both
-// reserves its records first: a record collection restarts the page cursor.
-static int reserve_pages(fs2_handle *h, int64_t need, PageAlloc *out) {
-    if (h->cursor + need > h->nfree) {
-        if (h->refs_live) return refs_short(h, "page");
-        int rc = collect(h, false);
-        if (rc) return rc;
-        if (need > h->nfree) {
-            const int64_t live = h->npool - h->nfree;
-            // by a quarter when the pool grows in place (cheap, no copy), else by half
-            const int64_t step = h->pool_vm.base ? h->npool / 4 : h->npool / 2;
-            rc = grow_pool(h, std::max(h->npool + step, live + 2 * need));
-            if (rc) return rc;
-        }
-    }
-    out->freel = h->freel;
-    out->base = h->cursor;
-    h->cursor += need;
-    return FS2_OK;
-}
-
-static int reserve_recs(fs2_handle *h, int64_t need, PageAlloc *out) {
-    if (h->rcursor + need > h->rnfree) {
-        if (h->refs_live) return refs_short(h, "record");
-        // a collection that cannot free enough is skipped: the pool grows at once
-        // (the free list keeps its taken entries, the new ids follow it)
-        const bool futile = h->rcollect_exact &&
-                            (h->rnfree - h->rcursor) + (h->rcursor - h->appends_since_rcollect) < need;
+// Reserve `need` free items of a pool (collecting, then growing it, when short);
+// *base is the reservation's first index into its free list.  A launch that needs
+// both reserves its records first: a record collection collects the pages too and
+// restarts the page cursor.  The pools differ in two places, both below.
+static int reserve(fs2_handle *h, Pool &p, int64_t need, int64_t *base) {
+    if (p.cursor + need > p.nfree) {
+        if (h->refs_live) return refs_short(h, p.name);
+        const bool recs = &p == &h->records;
+        // records only: a collection that cannot free enough is skipped and the pool
+        // grows at once (the free list keeps its taken entries, the new ids follow
+        // it).  The pages are always collected, and collect_body leaves their cursor
+        // at 0: for them the tests below are `need > nfree`, `live = n - nfree`.
+        const bool futile = recs && h->rcollect_exact && p.room() + (p.cursor - h->appends_since_rcollect) < need;
         int rc = FS2_OK;
         if (!futile) {
-            rc = collect(h, true);
+            rc = collect(h, recs);
             if (rc) return rc;
         }
-        if (h->rcursor + need > h->rnfree) {
-            const int64_t live = h->nrecs - (h->rnfree - h->rcursor);
-            // by a quarter in place, else by half; clamped to the id space (grow_recs
-            // fails beyond it)
-            const int64_t step = h->rpool_vm.base ? h->nrecs / 4 : h->nrecs / 2;
-            int64_t want = std::max(h->nrecs + step, live + 2 * need);
-            if (want > (int64_t)kRecIdLimit) want = std::max<int64_t>(kRecIdLimit, live + need);
-            rc = grow_recs(h, want);
+        if (p.cursor + need > p.nfree) {
+            const int64_t live = p.live();
+            // by a quarter when the pool grows in place (cheap, no copy), else by half
+            const int64_t step = p.vm.base ? p.n / 4 : p.n / 2;
+            int64_t want = std::max(p.n + step, live + 2 * need);
+            // records only: clamped to the id space; a page pool beyond it fails in grow
+            if (recs && want > p.id_limit) want = std::max<int64_t>(p.id_limit, live + need);
+            rc = grow(h, p, want);
             if (rc) return rc;
         }
     }
-    out->rfreel = h->rfreel;
-    out->rbase = h->rcursor;
-    h->rcursor += need;
+    *base = p.cursor;
+    p.cursor += need;
     return FS2_OK;
+}
+static int reserve_pages(fs2_handle *h, int64_t need, PageAlloc *out) {
+    const int rc = reserve(h, h->pages, need, &out->base);
+    out->freel = h->pages.freel;
+    return rc;
+}
+static int reserve_recs(fs2_handle *h, int64_t need, PageAlloc *out) {
+    const int rc = reserve(h, h->records, need, &out->rbase);
+    out->rfreel = h->records.freel;
+    return rc;
 }
 
 // An arena of at least `bytes` (grown by half again, the stream drained first:
@@ -1704,8 +1664,7 @@ static void free_handle(fs2_handle *h) {
     // next handle's first growth (hipMemCreate) waits for it -- 4 s in the round-4
     // driver bench (profiles/r04_g8_refs_growth_probe.txt; a device synchronize
     // between the sets of handles brought it back to milliseconds).
-    const bool vmm = h->pool_vm.base || h->rpool_vm.base || h->freel_vm.base || h->mark_vm.base ||
-                     h->rfreel_vm.base || h->rmark_vm.base;
+    const bool vmm = h->pages.mapped() || h->records.mapped();
     if (vmm) hipDeviceSynchronize();
     if (h->refs_shared && h->tp && !h->tp->in_process()) {
         // page_refs: no rank frees its pools while another may still read them (an
@@ -1727,17 +1686,9 @@ static void free_handle(fs2_handle *h) {
     hipFree(h->xt_key); hipFree(h->xt_ref); hipFree(h->xt_uidx); hipFree(h->xt_cmask); hipFree(h->xt_cbase);
     hipFree(h->xt_eslot); hipFree(h->xt_ulist);
     hipFree(h->sent_mask);
-    if (h->pool_vm.base) gm_free(h->pool_vm);
-    else hipFree(h->pool);
-    if (h->rpool_vm.base) gm_free(h->rpool_vm);
-    else hipFree(h->rpool);
-    if (h->freel_vm.base) gm_free(h->freel_vm); else hipFree(h->freel);
-    if (h->mark_vm.base) gm_free(h->mark_vm); else hipFree(h->mark);
-    if (h->rfreel_vm.base) gm_free(h->rfreel_vm); else hipFree(h->rfreel);
-    if (h->rmark_vm.base) gm_free(h->rmark_vm); else hipFree(h->rmark);
+    h->pages.release();
+    h->records.release();
     if (vmm) hipDeviceSynchronize();       // (the releases complete here, not at the next growth)
-    hipFree(h->bcnt); hipFree(h->nfree_dev);
-    hipFree(h->rbcnt); hipFree(h->rnfree_dev);
     hipFree(h->slb); hipFree(h->slb_pass); hipFree(h->ext_dev);
     hipFree(h->rank_d); hipFree(h->rank_e); hipFree(h->iblk);
     hipFree(h->mlo); hipFree(h->mhi); hipFree(h->out_src); hipFree(h->runs); hipFree(h->runs_n);
@@ -1871,8 +1822,8 @@ int fs2_create(const fs2_config *cfg, fs2_handle **out) {
         ok &= FS2_ALLOC(h->cnt[s], n * 4) == hipSuccess;
         ok &= FS2_ALLOC(h->bbox[s], nb * kBBoxRows * 4) == hipSuccess;
     }
-    ok &= FS2_ALLOC(h->nfree_dev, sizeof(int64_t)) == hipSuccess;
-    ok &= FS2_ALLOC(h->rnfree_dev, sizeof(int64_t)) == hipSuccess;
+    ok &= FS2_ALLOC(h->pages.nfree_dev, sizeof(int64_t)) == hipSuccess;
+    ok &= FS2_ALLOC(h->records.nfree_dev, sizeof(int64_t)) == hipSuccess;
     ok &= FS2_ALLOC(h->slb, sizeof(float)) == hipSuccess;
     ok &= FS2_ALLOC(h->slb_pass, sizeof(float)) == hipSuccess;
     ok &= FS2_ALLOC(h->ext_dev, sizeof(uint32_t)) == hipSuccess;
@@ -2052,11 +2003,11 @@ int fs2_create(const fs2_config *cfg, fs2_handle **out) {
             return fail(set_err(&h->err, FS2_ERR_ARG, "page_refs: needs 2..%d ranks and a page pool below %lld pages",
                                 kRefMaxRanks, (long long)lim));
     }
-    rc = grow_pool(h, npages);
+    rc = grow(h, h->pages, npages);
     if (rc) return fail(rc);
-    rc = grow_recs(h, cfg->record_pool > 0 ? cfg->record_pool
-                                            : n * h->cap + n * h->cap / 4 + 64 * n + recv_recs + 1024 +
-                                                  (h->refs ? 24 * n : 0));
+    rc = grow(h, h->records, cfg->record_pool > 0 ? cfg->record_pool
+                                                   : n * h->cap + n * h->cap / 4 + 64 * n + recv_recs + 1024 +
+                                                         (h->refs ? 24 * n : 0));
     if (rc) return fail(rc);
     if (G > 1) {
         // the sharded resample's buffers, made here rather than in a timed scan: the
@@ -2571,7 +2522,7 @@ int fs2_iterate_submit(fs2_handle *h, double rotation, double translation, const
         auto short_bits = [&]() -> uint8_t {
             const int64_t pneed = Mx * h->n + h->remote_bound();
             const int64_t rneed = Mx * h->n + (int64_t)kPageSlots * h->remote_bound();
-            return (uint8_t)((h->nfree - h->cursor < 2 * pneed ? 1 : 0) | (h->rnfree - h->rcursor < 2 * rneed ? 2 : 0));
+            return (uint8_t)((h->pages.room() < 2 * pneed ? 1 : 0) | (h->records.room() < 2 * rneed ? 2 : 0));
         };
         auto any_short = [&](uint8_t mine, uint8_t *all_or) -> int {
             uint8_t all[kMaxRanks] = {};
@@ -2604,8 +2555,8 @@ int fs2_iterate_submit(fs2_handle *h, double rotation, double translation, const
             const uint8_t mine = short_bits();
             const int64_t pneed = Mx * h->n + h->remote_bound();
             const int64_t rneed = Mx * h->n + (int64_t)kPageSlots * h->remote_bound();
-            rc = regrow_collective(h, (mine & 1) ? h->npool - (h->nfree - h->cursor) + 3 * pneed : 0,
-                                   (mine & 2) ? h->nrecs - (h->rnfree - h->rcursor) + 3 * rneed : 0);
+            rc = regrow_collective(h, (mine & 1) ? h->pages.live() + 3 * pneed : 0,
+                                   (mine & 2) ? h->records.live() + 3 * rneed : 0);
             if (rc) return rc;
         }
     }
@@ -2687,7 +2638,7 @@ int fs2_iterate_submit(fs2_handle *h, double rotation, double translation, const
     if (h->refs) {              // (also before references cross: this scan's resample may send them)
         const int64_t pneed = (int64_t)std::max(M, 1) * h->n + h->remote_bound();
         const int64_t rneed = (int64_t)std::max(M, 1) * h->n + (int64_t)kPageSlots * h->remote_bound();
-        const bool plow = h->nfree - h->cursor < 3 * pneed, rlow = h->rnfree - h->rcursor < 3 * rneed;
+        const bool plow = h->pages.room() < 3 * pneed, rlow = h->records.room() < 3 * rneed;
         want_collect = (plow || rlow) ? 1 : 0;
         // still short right after a collective collection: every rank grows next scan
         if (collected && plow) want_collect |= 2;
@@ -2739,8 +2690,8 @@ int fs2_iterate_submit(fs2_handle *h, double rotation, double translation, const
             // tail too short fails the scan loudly, fs2.h error_flags bit 3)
             const int64_t left = (int64_t)std::max(M - k0 - up.m, 0) * h->n;   // later passes' reservations
             LocalizeParams lp{};
-            lp.pcap = h->nfree - h->cursor - left;
-            lp.rcap = h->rnfree - h->rcursor - left;
+            lp.pcap = h->pages.room() - left;
+            lp.rcap = h->records.room() - left;
             lp.map = up.map;
             lp.cnt = up.cnt;
             lp.n = h->n;
@@ -2748,10 +2699,10 @@ int fs2_iterate_submit(fs2_handle *h, double rotation, double translation, const
             lp.m = up.m;
             lp.gate2f = up.gate2f;
             lp.meas = up.meas;
-            lp.freel = h->freel;
-            lp.ftail = h->nfree;
-            lp.rfreel = h->rfreel;
-            lp.rtail = h->rnfree;
+            lp.freel = h->pages.freel;
+            lp.ftail = h->pages.nfree;
+            lp.rfreel = h->records.freel;
+            lp.rtail = h->records.nfree;
             lp.stats = h->stats_dev;
             // one copy per distinct remote page: the page-dedup table the page
             // transfer would use (sized for every row of the shard, xfer_bufs), keys
@@ -2808,8 +2759,8 @@ static int complete_oldest(fs2_handle *h, double out_pose[3], fs2_iter_stats *st
     if (h->refs_shared) {
         // page_refs: the free lists' tails the localisations took; the remote row
         // entries left (recounted by a resample's gather); a collective collection next?
-        h->nfree -= (int64_t)st.loc_pages;
-        h->rnfree -= (int64_t)st.loc_recs;
+        h->pages.nfree -= (int64_t)st.loc_pages;
+        h->records.nfree -= (int64_t)st.loc_recs;
         h->remote_rows = st.resampled ? (int64_t)st.remote_rows
                                       : std::max<int64_t>(0, h->remote_rows - (int64_t)st.loc_rows);
         if (st.resampled) h->remote_pages = (int64_t)st.remote_pages;
@@ -2856,8 +2807,8 @@ static int complete_oldest(fs2_handle *h, double out_pose[3], fs2_iter_stats *st
         stats->cow_pages = st.cow_pages;
         stats->new_pages = st.new_pages;
         stats->collections = h->collections;
-        stats->pool_pages = (uint64_t)h->npool;
-        stats->pool_records = (uint64_t)h->nrecs;
+        stats->pool_pages = (uint64_t)h->pages.n;
+        stats->pool_records = (uint64_t)h->records.n;
         stats->pool_copies = h->vm_fallbacks;
         stats->pages_opened = st.opened;
         stats->reference_visits = st.ref_visits;

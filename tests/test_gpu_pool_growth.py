@@ -10,7 +10,8 @@ every measurement is a miss far from the maps (four new landmarks per particle
 and scan, no weight change, no resample to share records), so the live records
 grow by 4 N per scan and the pool must grow several times.  Every scan is
 compared with the C oracle, and no scan takes more than 1 ms longer than the
-median of its neighbours.
+median of its neighbours.  The page pool grows by the same code: its twin test
+starts it just above the maps and lets the appended pages grow it.
 """
 import os
 import time
@@ -81,6 +82,56 @@ def test_record_pool_grows_in_place(fail_relocate):
     for s in grew:
         nb = [ms_each[k] for k in range(max(1, s - 3), min(S, s + 4)) if k != s and k not in grew]
         assert ms_each[s] - float(np.median(nb)) < 1.0, (s, ms_each[s], nb, ms_each, pool)
+
+
+def test_page_pool_grows_in_place():
+    """The page pool's twin of test_record_pool_grows_in_place(False): the same four
+    far misses per scan and no resample, with a page pool just above the maps and the
+    record pool at its default.  N = 8192, L = 16, S = 24, page_pool = 8 N pages: the
+    live pages start at 2 N and grow by N / 2 per scan (four appends into pages of
+    eight slots), every scan reserves 4 N, and a growth goes to max(n + n / 4,
+    live + 2 * need), so the pool must grow about every eight to ten scans (measured:
+    65536 -> 106496 pages at scan 5, -> 147456 at scan 15).  Every scan is compared
+    with the C oracle; the pool grew in at least two scans and nothing was copied."""
+    import fast_slam_2
+    import fs2_synthetic as syn
+    from gpu_util import configure
+    from oracle import oracle as orc
+    configure()
+    N, L, S = 8192, 16, 24
+    cap = L + 4 * S + 8
+    wl = syn.Workload(N, L, seed=3)
+    x, y, yaw = wl.poses()
+    lm = wl.maps()
+    w = np.full(N, 1.0 / N)
+    cnt = np.full(N, L, np.int32)
+    f = fast_slam_2.FastSLAM2(N, rng="device", seed=4, landmark_capacity=cap, verbose=False, reduce="exact",
+                              record_assoc=True, page_pool=N * ((L + 7) // 8) + 6 * N)
+    f.set_state(x, y, yaw, w, cnt, lm)
+    o = orc.OracleFilter(N, cap)
+    o.set_state(x, y, yaw, w, cnt, lm)
+    rng = np.random.default_rng(12)
+    pages = []
+    for s in range(S):
+        rot, tr = syn.odometry(s)
+        # four misses, 20+ m from the maps and from each other
+        ms = np.array([[100.0 + 10.0 * s + 20.0 * k, 0.25 * k + 0.01 * s] for k in range(4)])
+        nz = rng.normal(0, 0.001 if rot else 0.0055, N)
+        u0 = rng.uniform(0, 1.0 / N)
+        pose, st = f.step(rot, tr, ms, None, nz, u0)
+        pages.append(st.pool_pages)
+        opose, oassoc, ors, one = o.iterate(rot, tr, ms, nz, u0)
+        assert np.array_equal(f.associations(), oassoc), s
+        assert bool(st.resampled) == ors, s
+        assert np.allclose(pose, opose, rtol=1e-9, atol=1e-12), s
+    fx, fy, fyaw, fw, fc, flm = f.get_state(lm_cap=cap)
+    assert np.array_equal(fc, o.cnt)
+    assert np.allclose(flm, o.lm, rtol=1e-9, atol=1e-12)
+    f.close()
+    grew = [s for s in range(1, S) if pages[s] > pages[s - 1]]
+    print(f"page pool per scan {pages}, grew at {grew}")
+    assert len(grew) >= 2, pages                        # the page pool grew inside the run
+    assert st.pool_copies == 0, st.pool_copies          # in place: nothing moved
 
 
 @pytest.mark.timeout(300)

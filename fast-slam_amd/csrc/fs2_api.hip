@@ -29,6 +29,7 @@
 #include "fs2_mtrng.hpp"
 #include "fs2_plan.hpp"
 #include "fs2_repr.hpp"
+#include "fs2_snapshot.hpp"
 
 using namespace fs2;
 static_assert(kMaxRanks <= fs2comm::kShmMaxRanks, "shm transport rank table");
@@ -3070,6 +3071,288 @@ int fs2_get_state(fs2_handle *h, int64_t first, int64_t count, double *x, double
         hipFree(stage);
         if (rc2) return rc2;
     }
+    return FS2_OK;
+}
+
+}  // extern "C"
+
+// -------------------------------------------------------------- snapshots ---
+// (format and validation: fs2_snapshot.hpp; kernels: fs2_snapshot.hip)
+
+namespace {
+
+// a device allocation of one call
+struct DevBuf {
+    void *p = nullptr;
+    ~DevBuf() { hipFree(p); }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 16)); }
+    template <typename T> T *as() const { return static_cast<T *>(p); }
+};
+
+constexpr int64_t kSnapPiece = 256ll << 20;      // the staging buffer: a transfer moves pieces of at most this
+
+int snap_begin(fs2_handle *h) {
+    if (!h) return set_err(nullptr, FS2_ERR_ARG, "null handle");
+    if (h->pending.on) return set_err(&h->err, FS2_ERR_STATE, "a submitted scan is pending (fs2_iterate_wait first)");
+    if (h->tp || h->cfg.world_size > 1 || h->cfg.sharded_path)
+        return set_err(&h->err, FS2_ERR_STATE, "snapshots need every particle on one rank (not the sharded path)");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const int rcm = mt_finish(h);        // a pending fs2_mt_draw was made for the state saved / replaced here
+    h->mt.armed = false;
+    if (rcm) return rcm;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return FS2_OK;
+}
+
+// bytes between host and device in pieces of at most kSnapPiece, ordered on the stream
+int snap_copy(fs2_handle *h, void *dst, const void *src, int64_t bytes, hipMemcpyKind kind) {
+    for (int64_t o = 0; o < bytes; o += kSnapPiece)
+        HIP_TRY(h, copy_sync(h, (char *)dst + o, (const char *)src + o, (size_t)std::min(kSnapPiece, bytes - o), kind));
+    return FS2_OK;
+}
+
+// The ids of a pool that carry its current epoch's mark, renumbered in id order:
+// tab [p.n] old id -> compact id, list [*live] the reverse.
+int snap_compact(fs2_handle *h, const Pool &p, DevBuf &tab, DevBuf &list, int64_t *live) {
+    hipStream_t s = h->stream;
+    const int64_t nb = collect_blocks(p.n);
+    DevBuf bcnt;
+    HIP_TRY(h, bcnt.alloc(sizeof(int64_t) * (size_t)(nb + 1)));
+    HIP_TRY(h, tab.alloc(sizeof(uint32_t) * (size_t)p.n));
+    HIP_TRY(h, launch_snap_count(p.mark, p.n, p.epoch, bcnt.as<int64_t>(), s));
+    HIP_TRY(h, launch_sweep_scan(bcnt.as<int64_t>(), nb, bcnt.as<int64_t>() + nb, s));
+    HIP_TRY(h, copy_sync(h, live, bcnt.as<int64_t>() + nb, sizeof(int64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(h, list.alloc(sizeof(uint32_t) * (size_t)*live));
+    HIP_TRY(h, launch_snap_table(p.mark, p.n, p.epoch, bcnt.as<int64_t>(), tab.as<uint32_t>(), list.as<uint32_t>(), s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return FS2_OK;
+}
+
+int snap_check_host(const void *buf, int64_t size, SnapHeader *hdr, int32_t *max_count) {
+    if (!buf || size < kSnapHeaderBytes) return kSnapShort;
+    std::memcpy(hdr, buf, sizeof *hdr);
+    if (const int code = snap_check_header(*hdr, size)) return code;
+    // the count rules alone (what sizes a restore's buffers)
+    const char *cs = (const char *)buf + hdr->sec[kSnapScalars][0] + 32 * hdr->n;
+    int32_t mx = 0;
+    for (int64_t i = 0; i < hdr->n; ++i) {
+        int32_t c;
+        std::memcpy(&c, cs + 4 * i, 4);
+        if (c < 0 || c > 8 * hdr->rows || c > hdr->cnt_upper) return kSnapCnt;
+        mx = std::max(mx, c);
+    }
+    if ((mx + kPageSlots - 1) / kPageSlots != hdr->rows) return kSnapRowsExact;
+    *max_count = mx;
+    return kSnapOk;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fs2_snapshot_check(const void *buf, int64_t size, fs2_snapshot_info *info) {
+    SnapHeader hd;
+    int32_t mx = 0;
+    int code = snap_check_host(buf, size, &hd, &mx);
+    if (code == kSnapOk) {
+        // sections start on 64-byte boundaries, but buf itself may sit anywhere: the
+        // 4-byte fields are read in place only from an aligned buffer
+        std::vector<char> copy;
+        const char *b = (const char *)buf;
+        if ((uintptr_t)b % 8) {
+            copy.assign(b, b + size);
+            b = copy.data();
+        }
+        SnapView v{hd.n, hd.rows, hd.pages, hd.records, hd.cnt_upper,
+                   (const int32_t *)(b + hd.sec[kSnapScalars][0] + 32 * hd.n),
+                   (const uint32_t *)(b + hd.sec[kSnapRows][0]), hd.n, b + hd.sec[kSnapPages][0], nullptr};
+        std::vector<uint32_t> owners((size_t)hd.pages, 0u);
+        std::vector<uint8_t> shared((size_t)hd.pages, 0);
+        uint32_t full = 0;
+        code = snap_check_particles(v, 0, hd.n, 0, owners.data(), shared.data(), &full);
+        if (code == kSnapOk) code = snap_check_particles(v, 0, hd.n, 1, owners.data(), shared.data(), &full);
+    }
+    if (code != kSnapOk) return set_err(nullptr, FS2_ERR_ARG, "invalid snapshot: %s", snap_error_text(code));
+    if (info)
+        *info = fs2_snapshot_info{hd.total, hd.n, hd.rows, hd.pages, hd.records, mx, hd.scan, (int32_t)hd.version, 0};
+    return FS2_OK;
+}
+
+int fs2_snapshot_save(fs2_handle *h, void *buf, int64_t capacity, int64_t *size) {
+    if (int rc = snap_begin(h)) return rc;
+    if (!size) return set_err(&h->err, FS2_ERR_ARG, "fs2_snapshot_save: size is null");
+    hipStream_t s = h->stream;
+    const int c = h->cur;
+    Pool &p = h->pages, &r = h->records;
+    const MapRef map = h->map();
+    // the live pages and records, from the pools' marks at a fresh epoch: nothing is
+    // swept, so the free lists, their cursors and the next collection are as before
+    HIP_TRY(h, p.next_epoch(s));
+    HIP_TRY(h, launch_collect_mark(map, h->cnt[c], p.mark, p.epoch, nullptr, s));
+    HIP_TRY(h, r.next_epoch(s));
+    HIP_TRY(h, launch_mark_records(p.data, p.n, p.mark, p.epoch, r.n, r.mark, r.epoch, s));
+    DevBuf ptab, plist, rtab, rlist;
+    int64_t U = 0, C = 0;
+    if (int rc = snap_compact(h, p, ptab, plist, &U)) return rc;
+    if (int rc = snap_compact(h, r, rtab, rlist, &C)) return rc;
+    std::vector<int32_t> hc((size_t)h->n);
+    HIP_TRY(h, copy_sync(h, hc.data(), h->cnt[c], sizeof(int32_t) * (size_t)h->n, hipMemcpyDeviceToHost));
+    int32_t mx = 0;
+    for (int32_t v : hc) mx = std::max(mx, v);
+    const int R = (mx + kPageSlots - 1) / kPageSlots;
+
+    SnapHeader hd{};
+    std::memcpy(hd.magic, "FS2SNAP", 8);
+    hd.version = kSnapVersion;
+    hd.header_bytes = kSnapHeaderBytes;
+    hd.page_slots = kPageSlots;
+    hd.page_bytes = kPageBytes;
+    hd.rec_bytes = kRecBytes;
+    hd.cnt_upper = std::max(h->cnt_upper, mx);
+    hd.n = h->n;
+    hd.rows = R;
+    hd.pages = U;
+    hd.records = C;
+    hd.scan = h->scan;
+    hd.org = h->frame.org;
+    hd.cell = h->frame.cell;
+    hd.ext_seen = h->ext_seen;
+    hd.total = snap_layout(h->n, R, U, C, hd.sec);
+    *size = hd.total;
+    if (!buf) return FS2_OK;
+    if (capacity < hd.total)
+        return set_err(&h->err, FS2_ERR_ARG, "snapshot buffer too small (%lld < %lld)", (long long)capacity,
+                       (long long)hd.total);
+    HIP_TRY(h, copy_sync(h, &hd.slb, h->slb, sizeof(float), hipMemcpyDeviceToHost));
+    char *out = (char *)buf;
+    std::memcpy(out, &hd, sizeof hd);
+    for (int k = 0; k < kSnapSections; ++k) {        // pad bytes
+        const int64_t end = hd.sec[k][0] + hd.sec[k][1];
+        std::memset(out + end, 0, (size_t)((k + 1 < kSnapSections ? hd.sec[k + 1][0] : hd.total) - end));
+    }
+    // scalars, straight from the current buffer set
+    {
+        char *q = out + hd.sec[kSnapScalars][0];
+        const double *src[4] = {h->x[c], h->y[c], h->yaw[c], h->w[c]};
+        for (int k = 0; k < 4; ++k)
+            if (int rc = snap_copy(h, q + 8 * h->n * k, src[k], 8 * h->n, hipMemcpyDeviceToHost)) return rc;
+        std::memcpy(q + 32 * h->n, hc.data(), sizeof(int32_t) * (size_t)h->n);
+    }
+    // rows, pages and records through the staging buffer, a piece at a time
+    const int64_t row_bytes = 4 * h->n;
+    const int64_t rows_per = std::max<int64_t>(1, kSnapPiece / row_bytes);
+    const int64_t pages_per = kSnapPiece / kPageBytes, recs_per = kSnapPiece / kRecBytes;
+    const int64_t stage_bytes = std::max(std::max(std::min<int64_t>(rows_per, R) * row_bytes,
+                                                  std::min(pages_per, U) * kPageBytes),
+                                         std::min(recs_per, C) * kRecBytes);
+    DevBuf stage;
+    HIP_TRY(h, stage.alloc((size_t)stage_bytes));
+    for (int64_t r0 = 0; r0 < R; r0 += rows_per) {
+        const int64_t k = std::min<int64_t>(rows_per, R - r0);
+        HIP_TRY(h, launch_snap_rows(map, h->cnt[c], ptab.as<uint32_t>(), p.n, (int)r0, (int)k, stage.as<uint32_t>(), s));
+        HIP_TRY(h, copy_sync(h, out + hd.sec[kSnapRows][0] + r0 * row_bytes, stage.p, (size_t)(k * row_bytes),
+                             hipMemcpyDeviceToHost));
+    }
+    for (int64_t k0 = 0; k0 < U; k0 += pages_per) {
+        const int64_t k = std::min(pages_per, U - k0);
+        HIP_TRY(h, launch_snap_gather(p.data, plist.as<uint32_t>() + k0, k, kPageBytes / 16, rtab.as<uint32_t>(), r.n,
+                                      stage.p, s));
+        HIP_TRY(h, copy_sync(h, out + hd.sec[kSnapPages][0] + k0 * kPageBytes, stage.p, (size_t)(k * kPageBytes),
+                             hipMemcpyDeviceToHost));
+    }
+    for (int64_t k0 = 0; k0 < C; k0 += recs_per) {
+        const int64_t k = std::min(recs_per, C - k0);
+        HIP_TRY(h, launch_snap_gather(r.data, rlist.as<uint32_t>() + k0, k, kRecBytes / 16, nullptr, 0, stage.p, s));
+        HIP_TRY(h, copy_sync(h, out + hd.sec[kSnapRecords][0] + k0 * kRecBytes, stage.p, (size_t)(k * kRecBytes),
+                             hipMemcpyDeviceToHost));
+    }
+    return FS2_OK;
+}
+
+int fs2_snapshot_load(fs2_handle *h, const void *buf, int64_t size) {
+    if (int rc = snap_begin(h)) return rc;
+    SnapHeader hd;
+    int32_t mx = 0;
+    if (const int code = snap_check_host(buf, size, &hd, &mx))
+        return set_err(&h->err, FS2_ERR_ARG, "invalid snapshot: %s", snap_error_text(code));
+    if (hd.n != h->n)
+        return set_err(&h->err, FS2_ERR_ARG, "snapshot of %lld particles, handle of %lld", (long long)hd.n,
+                       (long long)h->n);
+    if (!(hd.cell > 0.0f) || !std::isfinite(hd.cell) || !std::isfinite(hd.org) || !(hd.ext_seen >= 0.0f) ||
+        std::isnan(hd.slb))
+        return set_err(&h->err, FS2_ERR_ARG, "invalid snapshot: summary grid or mirror bound is not a number");
+    const char *in = (const char *)buf;
+    const int64_t N = hd.n, U = hd.pages, C = hd.records;
+    const int R = (int)hd.rows;
+    // room: rows for the longest map (FS2_ERR_CAPACITY past the handle's limit), then
+    // C records and U pages (the records first: their collection restarts the page
+    // cursor).  All of it leaves the state as it is.
+    if (int rc = grow_rows(h, hd.cnt_upper)) return rc;      // (>= every map size: snap_check_host)
+    PageAlloc pa{};
+    if (int rc = reserve_recs(h, C, &pa)) return rc;
+    if (int rc = reserve_pages(h, U, &pa)) return rc;
+    hipStream_t s = h->stream;
+    const int c = h->cur, o = 1 - c;
+    Pool &p = h->pages, &r = h->records;
+    const uint32_t *pids = pa.freel + pa.base, *rids = pa.rfreel + pa.rbase;
+    // counts and rows wait in the other buffer set; pages and records go to their
+    // reserved (free) ids: nothing the handle reads has changed yet
+    if (int rc = snap_copy(h, h->cnt[o], in + hd.sec[kSnapScalars][0] + 32 * N, 4 * N, hipMemcpyHostToDevice)) return rc;
+    if (int rc = snap_copy(h, h->pt[o], in + hd.sec[kSnapRows][0], 4 * N * R, hipMemcpyHostToDevice)) return rc;
+    const int64_t pages_per = kSnapPiece / kPageBytes, recs_per = kSnapPiece / kRecBytes;
+    DevBuf stage, owners, shared, flags;
+    HIP_TRY(h, stage.alloc((size_t)std::max(std::min(pages_per, U) * kPageBytes, std::min(recs_per, C) * kRecBytes)));
+    for (int64_t k0 = 0; k0 < U; k0 += pages_per) {
+        const int64_t k = std::min(pages_per, U - k0);
+        HIP_TRY(h, copy_sync(h, stage.p, in + hd.sec[kSnapPages][0] + k0 * kPageBytes, (size_t)(k * kPageBytes),
+                             hipMemcpyHostToDevice));
+        HIP_TRY(h, launch_snap_scatter(stage.p, pids + k0, k, kPageBytes / 16, p.data, s));
+        HIP_TRY(h, hipStreamSynchronize(s));         // (the next piece overwrites the staging buffer)
+    }
+    for (int64_t k0 = 0; k0 < C; k0 += recs_per) {
+        const int64_t k = std::min(recs_per, C - k0);
+        HIP_TRY(h, copy_sync(h, stage.p, in + hd.sec[kSnapRecords][0] + k0 * kRecBytes, (size_t)(k * kRecBytes),
+                             hipMemcpyHostToDevice));
+        HIP_TRY(h, launch_snap_scatter(stage.p, rids + k0, k, kRecBytes / 16, r.data, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+    }
+    // the check kernel on what is installed (host and device run snap_check_particles)
+    HIP_TRY(h, owners.alloc(sizeof(uint32_t) * (size_t)U));
+    HIP_TRY(h, shared.alloc((size_t)U));
+    HIP_TRY(h, flags.alloc(2 * sizeof(uint32_t)));
+    HIP_TRY(h, hipMemsetAsync(owners.p, 0, sizeof(uint32_t) * (size_t)U, s));
+    HIP_TRY(h, hipMemsetAsync(shared.p, 0, (size_t)U, s));
+    HIP_TRY(h, hipMemsetAsync(flags.p, 0, 2 * sizeof(uint32_t), s));
+    const SnapView v{N, R, U, C, hd.cnt_upper, h->cnt[o], h->pt[o], N, p.data, pids};
+    HIP_TRY(h, launch_snap_check(v, 0, owners.as<uint32_t>(), shared.as<uint8_t>(), flags.as<uint32_t>(), s));
+    HIP_TRY(h, launch_snap_check(v, 1, owners.as<uint32_t>(), shared.as<uint8_t>(), flags.as<uint32_t>(), s));
+    uint32_t fl[2] = {0, 0};
+    HIP_TRY(h, copy_sync(h, fl, flags.p, sizeof fl, hipMemcpyDeviceToHost));
+    if (fl[0] || (R > 0 && !fl[1]))
+        return set_err(&h->err, FS2_ERR_ARG, "invalid snapshot: %s",
+                       snap_error_text(fl[0] ? (int)fl[0] : (int)kSnapRowsExact));
+    // commit: mirrors and row entries renumbered to the pool ids, the rows into the
+    // live page table; scalars, counters and the summary grid; the row boxes rebuilt
+    HIP_TRY(h, launch_snap_commit(p.data, pids, U, rids, C, h->pt[o], h->pt[c], N, R, h->cnt[o], s));
+    HIP_TRY(h, hipMemcpyAsync(h->cnt[c], h->cnt[o], sizeof(int32_t) * (size_t)N, hipMemcpyDeviceToDevice, s));
+    {
+        const char *q = in + hd.sec[kSnapScalars][0];
+        double *dst[4] = {h->x[c], h->y[c], h->yaw[c], h->w[c]};
+        for (int k = 0; k < 4; ++k)
+            if (int rc = snap_copy(h, dst[k], q + 8 * N * k, 8 * N, hipMemcpyHostToDevice)) return rc;
+    }
+    HIP_TRY(h, copy_sync(h, h->slb, &hd.slb, sizeof(float), hipMemcpyHostToDevice));
+    h->frame = SumFrame{hd.org, hd.cell, 1.0f / hd.cell};
+    h->ext_seen = hd.ext_seen;
+    h->scan = hd.scan;
+    h->cnt_upper = hd.cnt_upper;
+    // the collection bound (reserve): the installed records are live, the records of
+    // the maps replaced are of unknown number
+    h->appends_since_rcollect += C;
+    h->rcollect_exact = false;
+    h->imported.assign((size_t)h->n, 1);
+    HIP_TRY(h, launch_bbox_build(h->map(), h->cnt[c], s));
+    HIP_TRY(h, hipStreamSynchronize(s));
     return FS2_OK;
 }
 

@@ -766,6 +766,34 @@ hipError_t launch_collect_records(const char *pool, int64_t npool, const uint8_t
                                   int64_t nrecs, uint8_t *rmark, uint8_t repoch, int64_t *rbcnt,
                                   uint32_t *rfreel, int64_t *rnfree_dev, hipStream_t s);
 int64_t collect_blocks(int64_t npool);
+// the halves of launch_collect_records a snapshot uses: the record marks alone (no
+// sweep: the free list stays), and the sweep's scan of nb block counts (*total: their sum)
+hipError_t launch_mark_records(const char *pool, int64_t npool, const uint8_t *mark, uint8_t epoch, int64_t nrecs,
+                               uint8_t *rmark, uint8_t repoch, hipStream_t s);
+hipError_t launch_sweep_scan(int64_t *bcnt, int64_t nb, int64_t *total, hipStream_t s);
+
+// compact snapshots (fs2_snapshot.hip; format and validation: fs2_snapshot.hpp).
+// Save: the ids marked `epoch` counted per collect_blocks block into bcnt, then (bcnt
+// scanned) tab[old id] = compact id or 0xffffffff and list[compact id] = old id; the
+// page table's rows [r0, r0 + nrows) renumbered through ptab; items ids[0 .. k) of a
+// pool of L x 16-byte items gathered into out (rtab: the mirrors' record ids renumbered).
+hipError_t launch_snap_count(const uint8_t *mark, int64_t npool, uint8_t epoch, int64_t *bcnt, hipStream_t s);
+hipError_t launch_snap_table(const uint8_t *mark, int64_t npool, uint8_t epoch, const int64_t *bcnt, uint32_t *tab,
+                             uint32_t *list, hipStream_t s);
+hipError_t launch_snap_rows(MapRef map, const int32_t *cnt, const uint32_t *ptab, int64_t npool, int r0, int nrows,
+                            uint32_t *out, hipStream_t s);
+hipError_t launch_snap_gather(const char *pool, const uint32_t *ids, int64_t k, int L, const uint32_t *rtab,
+                              int64_t nrecs, void *out, hipStream_t s);
+// Restore: item j of `in` to pool id ids[j]; one pass (0, then 1) of snap_check_particles
+// over every particle (owners [U], shared [U], flags [2] zeroed by the caller: flags[0]
+// the first violated rule, flags[1] set when a map needs all R rows); then the installed
+// pages' record ids and the rows src -> dst renumbered to the pool ids pids / rids.
+struct SnapView;
+hipError_t launch_snap_scatter(const void *in, const uint32_t *ids, int64_t k, int L, char *pool, hipStream_t s);
+hipError_t launch_snap_check(const SnapView &v, int pass, uint32_t *owners, uint8_t *shared, uint32_t *flags,
+                             hipStream_t s);
+hipError_t launch_snap_commit(char *pool, const uint32_t *pids, int64_t U, const uint32_t *rids, int64_t C,
+                              const uint32_t *src, Desc *dst, int64_t n, int R, const int32_t *cnt, hipStream_t s);
 
 // known-landmark clustering (fs2_cluster.hip).  status: 0 ok, 1 non-finite input,
 // 2 coordinate span too large.

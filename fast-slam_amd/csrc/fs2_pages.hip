@@ -60,32 +60,6 @@ __global__ __launch_bounds__(kBlock) void k_mark(const MapRef map, const int32_t
     if (__any(remote)) __threadfence_system();
 }
 
-__device__ __forceinline__ int wave_incl_scan_int(int v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(v, d, 64);
-        if (lane >= d) v += o;
-    }
-    return v;
-}
-
-// exclusive prefix of v over the workgroup (kBlock threads); total in *tot
-__device__ __forceinline__ int block_excl_scan(int v, int *lds, int *tot) {
-    const int inc = wave_incl_scan_int(v);
-    const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 63) lds[wid] = inc;
-    __syncthreads();
-    int off = 0, t = 0;
-#pragma unroll
-    for (int k = 0; k < kBlock / 64; ++k) {
-        if (k < wid) off += lds[k];
-        t += lds[k];
-    }
-    *tot = t;
-    return off + inc - v;
-}
-
 // free ids among the kSweepPer consecutive ids from id0 (bit e: id0 + e), from
 // one 16-byte load of their marks; ids past npool are not free
 __device__ __forceinline__ unsigned free_bits(const uint8_t *mark, int64_t npool, uint8_t epoch,
@@ -216,15 +190,25 @@ hipError_t launch_collect_records(const char *pool, int64_t npool, const uint8_t
                                   int64_t nrecs, uint8_t *rmark, uint8_t repoch, int64_t *rbcnt,
                                   uint32_t *rfreel, int64_t *rnfree_dev, hipStream_t s) {
     const int64_t nb = collect_blocks(nrecs);
-    const int64_t lanes = npool * kPageSlots;
-    if (lanes > 0) {
-        const int64_t grid = std::min<int64_t>((lanes + kBlock - 1) / kBlock, kMarkRecsGrid);
-        hipLaunchKernelGGL(k_mark_recs, dim3((unsigned)grid), dim3(kBlock), 0, s, pool, npool, mark, epoch, nrecs,
-                           rmark, repoch);
-    }
+    (void)launch_mark_records(pool, npool, mark, epoch, nrecs, rmark, repoch, s);   // (hipGetLastError below)
     hipLaunchKernelGGL(k_sweep_count, dim3((unsigned)nb), dim3(kBlock), 0, s, rmark, nrecs, repoch, rbcnt);
     hipLaunchKernelGGL(k_sweep_scan, dim3(1), dim3(1024), 0, s, rbcnt, nb, rnfree_dev);
     hipLaunchKernelGGL(k_sweep_write, dim3((unsigned)nb), dim3(kBlock), 0, s, rmark, nrecs, repoch, rbcnt, rfreel);
+    return hipGetLastError();
+}
+
+hipError_t launch_mark_records(const char *pool, int64_t npool, const uint8_t *mark, uint8_t epoch, int64_t nrecs,
+                               uint8_t *rmark, uint8_t repoch, hipStream_t s) {
+    const int64_t lanes = npool * kPageSlots;
+    if (lanes <= 0) return hipSuccess;
+    const int64_t grid = std::min<int64_t>((lanes + kBlock - 1) / kBlock, kMarkRecsGrid);
+    hipLaunchKernelGGL(k_mark_recs, dim3((unsigned)grid), dim3(kBlock), 0, s, pool, npool, mark, epoch, nrecs, rmark,
+                       repoch);
+    return hipGetLastError();
+}
+
+hipError_t launch_sweep_scan(int64_t *bcnt, int64_t nb, int64_t *total, hipStream_t s) {
+    hipLaunchKernelGGL(k_sweep_scan, dim3(1), dim3(1024), 0, s, bcnt, nb, total);
     return hipGetLastError();
 }
 

@@ -282,6 +282,34 @@ __device__ int block_max_i(int v, int *lds) {
     return t;
 }
 
+// ---- integer scans over a workgroup of kBlock threads (pool sweeps, snapshots) ----
+
+__device__ __forceinline__ int wave_incl_scan_int(int v) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int o = __shfl_up(v, d, 64);
+        if (lane >= d) v += o;
+    }
+    return v;
+}
+
+// exclusive prefix of v over the workgroup (kBlock threads); total in *tot
+__device__ __forceinline__ int block_excl_scan(int v, int *lds, int *tot) {
+    const int inc = wave_incl_scan_int(v);
+    const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 63) lds[wid] = inc;
+    __syncthreads();
+    int off = 0, t = 0;
+#pragma unroll
+    for (int k = 0; k < kBlock / 64; ++k) {
+        if (k < wid) off += lds[k];
+        t += lds[k];
+    }
+    *tot = t;
+    return off + inc - v;
+}
+
 // ------------------------------------------------------------- map access ---
 
 typedef int v4i __attribute__((ext_vector_type(4)));

@@ -165,6 +165,15 @@ class fs2_mt_state(C.Structure):
                 int(self.has_gauss), float(self.gauss))
 
 
+class fs2_snapshot_info(C.Structure):
+    _fields_ = [("bytes", C.c_int64), ("num_particles", C.c_int64), ("rows", C.c_int64), ("pages", C.c_int64),
+                ("records", C.c_int64), ("max_count", C.c_int64), ("scan", C.c_uint64),
+                ("version", C.c_int32), ("reserved0", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
+
+
 class FS2Error(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libfs2 error {code}: {msg}")
@@ -196,6 +205,9 @@ SIGNATURES = [
                                 C.c_int32]),
     ("fs2_set_state", C.c_int, [_H, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int32,
                                 C.c_int32]),
+    ("fs2_snapshot_save", C.c_int, [_H, _vp, C.c_int64, C.POINTER(C.c_int64)]),
+    ("fs2_snapshot_load", C.c_int, [_H, _vp, C.c_int64]),
+    ("fs2_snapshot_check", C.c_int, [_vp, C.c_int64, C.POINTER(fs2_snapshot_info)]),
     ("fs2_get_assoc", C.c_int, [_H, _ip, C.c_int64, _ip]),
     ("fs2_shard_info", C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                  C.POINTER(C.c_int32)]),

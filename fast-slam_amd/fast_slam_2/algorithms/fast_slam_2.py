@@ -52,7 +52,7 @@ class FastSLAM2:
                  landmark_capacity: int = 64, rank: int = 0, world_size: int = 1,
                  comm_id: bytes | None = None, verbose: bool = True, gate_filter: bool = True,
                  comm_mode: str = "rccl", sharded_path: bool = False, page_pool: int = 0,
-                 record_pool: int = 0, page_refs: str = "auto"):
+                 record_pool: int = 0, page_refs: str = "auto", max_landmark_capacity: int = 0):
         lib = nat.load()
         cfg = nat.default_config()
         cfg.num_particles = int(config.NUM_PARTICLES if num_particles is None else num_particles)
@@ -63,6 +63,7 @@ class FastSLAM2:
             cfg.measurement_noise[k] = R[k]
         cfg.max_landmark_distance = float(config.MAXIMUM_LANDMARK_DISTANCE)
         cfg.landmark_capacity = int(landmark_capacity)
+        cfg.max_landmark_capacity = int(max_landmark_capacity)   # hard limit on map slots (0: 4096)
         cfg.device = int(device)
         cfg.reduce_mode = _REDUCE[reduce]
         if seed is not None:
@@ -294,6 +295,45 @@ class FastSLAM2:
                                           nat.ptr(cnth), nat.ptr(lmh), cap, nat.FS2_HOST),
                   self._h)
         self._particles = None
+
+    # ------------------------------------------------------------ snapshots
+    def snapshot(self) -> np.ndarray:
+        """The filter as one uint8 array (fs2_snapshot_save): particles, maps and the scan
+        counter in the device's own compact form -- every distinct page and record once, so
+        maps that resampled siblings share are stored once -- for `restore` to resume the run
+        bit for bit.  One sizing call, then one save into a single allocation.
+
+        With rng="numpy" or rng="numpy-host" the generator's state belongs to the caller:
+        keep np.random.get_state() next to the snapshot and np.random.set_state() it before
+        resuming.  rng="device" draws from (seed, scan counter), which the snapshot holds."""
+        size = C.c_int64()
+        nat.check(self._lib.fs2_snapshot_save(self._h, None, 0, C.byref(size)), self._h)
+        out = np.empty(size.value, dtype=np.uint8)
+        nat.check(self._lib.fs2_snapshot_save(self._h, out.ctypes.data, out.size, C.byref(size)), self._h)
+        return out
+
+    def restore(self, buf) -> None:
+        """Replace this filter's particles, maps and scan counter with a snapshot's
+        (fs2_snapshot_load; any object with the buffer protocol).  The snapshot must be of
+        the same particle count; it is validated completely first and an invalid one leaves
+        the filter unchanged.  This filter keeps its own configuration (noise, gate, seed,
+        reduce mode): resume with the arguments the snapshot's filter was made with.
+
+        With rng="numpy" or rng="numpy-host" restore np.random's state yourself
+        (np.random.set_state(saved)); see `snapshot`."""
+        a = np.frombuffer(buf, dtype=np.uint8)
+        nat.check(self._lib.fs2_snapshot_load(self._h, a.ctypes.data, a.size), self._h)
+        self._particles = None
+
+    @staticmethod
+    def snapshot_info(buf) -> dict:
+        """Validate a snapshot on the host (no device) and describe it: bytes,
+        num_particles, rows, pages, records, max_count, scan, version.  Raises FS2Error
+        (FS2_ERR_ARG) naming the first violated rule."""
+        a = np.frombuffer(buf, dtype=np.uint8)
+        info = nat.fs2_snapshot_info()
+        nat.check(nat.load().fs2_snapshot_check(a.ctypes.data, a.size, C.byref(info)))
+        return info.as_dict()
 
     @property
     def particles(self) -> "ParticleView":

@@ -320,6 +320,34 @@ int fs2_set_state(fs2_handle *h, int64_t first, int64_t count, const double *x,
                   const double *y, const double *yaw, const double *w, const int32_t *cnt,
                   const double *lm, int32_t lm_cap, int32_t where);
 
+/* Compact snapshots: a handle's particles, maps and scan counter as the device holds
+ * them -- the page table with its entries renumbered, each distinct live page once,
+ * each distinct live record once (pages shared by resampled siblings stay shared) --
+ * for stopping a run and resuming it bit for bit.  The byte layout and what makes a
+ * snapshot valid: csrc/fs2_snapshot.hpp, DESIGN.md §13.  Preconditions as
+ * fs2_get_state: FS2_ERR_STATE while scans are outstanding; a pending deferred draw is
+ * ended first; the handle's stream is synchronised.  Handles that run the sharded path
+ * (world_size > 1 or sharded_path) return FS2_ERR_STATE. */
+typedef struct fs2_snapshot_info {
+    int64_t bytes, num_particles, rows, pages, records, max_count; uint64_t scan;
+    int32_t version, reserved0;
+} fs2_snapshot_info;
+
+/* buf == NULL: sizing only; *size always receives the exact byte count;
+ * capacity < *size -> FS2_ERR_ARG, nothing written (as fs2_particles_json).
+ * A save changes nothing a later scan or pool collection sees. */
+int fs2_snapshot_save(fs2_handle *h, void *buf, int64_t capacity, int64_t *size);
+/* Replaces the handle's particles, maps and scan counter (with cnt_upper, the summary
+ * grid and the mirror bound); the handle's own configuration (noise, gate, seed,
+ * reduce mode) stays.  The snapshot is validated completely first; on any error the
+ * handle is unchanged.  FS2_ERR_ARG: invalid, or of another particle count;
+ * FS2_ERR_CAPACITY: a map exceeds max_landmark_capacity.  With the numpy generators the
+ * generator state is the caller's (np.random.get_state()), not part of the snapshot. */
+int fs2_snapshot_load(fs2_handle *h, const void *buf, int64_t size);
+/* Host-only validation (no device needed): FS2_OK and *info, or FS2_ERR_ARG with the
+ * first violated rule in fs2_last_error(NULL). */
+int fs2_snapshot_check(const void *buf, int64_t size, fs2_snapshot_info *info);
+
 /* Association index per (measurement, local particle) of the last scan,
  * [M][N_local] row-major; -1 = no landmark associated (a new one was appended).
  * The particles are those of the scan's update pass, before its resample (a

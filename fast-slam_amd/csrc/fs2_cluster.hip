@@ -3,7 +3,16 @@
 // sklearn DBSCAN; called by LandmarkUtils.update_known_landmarks,
 // fast_slam_2/utils/landmark_utils.py:120-144, over every landmark of every particle).
 //
-// sklearn's result, restated as a deterministic function of the points:
+// The labels equal sklearn's wherever sklearn tests a pair point by point.  sklearn's
+// KD-tree also accepts a whole node without per-point tests when a square-rooted
+// bound on the node's farthest corner is <= eps, so within about an ulp of eps its
+// answer depends on how its tree happens to split the input (on a two-point input
+// the node's far corner is the other point).  libfs2 applies the per-point predicate
+// below everywhere; the tie_two_point cases of tests/golden/cluster_edges.npz
+// (gen_cluster_edges.py) record inputs on which the two differ, its tie_groups cases
+// near-ties on which they agree.
+//
+// sklearn's per-point result, restated as a deterministic function of the points:
 //   neighbour(p, q)  <=>  fl(fl(dx*dx) + fl(dy*dy)) <= fl(eps*eps)   (p itself counts);
 //   core(p)          <=>  |{q : neighbour(p, q)}| >= min_samples;
 //   clusters         =   connected components of the core points under neighbour,

@@ -517,9 +517,13 @@ int fs2_debug_mt_jump(const uint32_t key[624], uint64_t J, uint32_t out[624]);
 
 /* Replaces GeometryUtils.cluster_points (utils/geometry_utils.py:26-62), i.e.
  * sklearn DBSCAN(eps, min_samples) over n points (x, y) followed by the centre
- * (numpy mean) of every cluster, clusters in sklearn's label order.  Exact:
- * labels equal sklearn's (border points to the lowest-numbered cluster in reach).
- * centres is [cap][2]; K > cap sets *n_clusters = K and fails with FS2_ERR_ARG.
+ * (numpy mean) of every cluster, clusters in sklearn's label order.  Labels equal
+ * sklearn's wherever sklearn tests the pair point by point (border points to the
+ * lowest-numbered cluster in reach): neighbour <=> fl(fl(dx*dx) + fl(dy*dy)) <=
+ * fl(eps*eps), applied to every pair.  sklearn's KD-tree also accepts whole nodes on
+ * a square-rooted bound, so its own answer within about an ulp of eps depends on its
+ * tree; the tie_two_point cases of tests/golden/cluster_edges.npz record the
+ * difference.  centres is [cap][2]; K > cap sets *n_clusters = K and fails with FS2_ERR_ARG.
  * labels (nullable) receives n labels, -1 = noise.  where: FS2_HOST / FS2_DEVICE
  * for points, centres and labels.  Non-finite input fails (sklearn raises). */
 int fs2_cluster_points(int32_t device, const double *points, int64_t n, double eps,

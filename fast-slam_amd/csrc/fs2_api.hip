@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <new>
 #include <string>
 #include <thread>
 #include <tuple>
@@ -3146,6 +3147,135 @@ int snap_check_host(const void *buf, int64_t size, SnapHeader *hdr, int32_t *max
     return kSnapOk;
 }
 
+// fs2_snapshot_save (idx null: every particle in place, m == h->n) and
+// fs2_snapshot_save_select (particles idx[0 .. m), a host pointer), after snap_begin.
+// The two differ in what is marked and in how the per-particle sections are read (the
+// selection's through idx, fs2_snapshot.hip); header, compaction, pages and records are
+// one code.  Besides the id tables, the block counts and the staging buffer a selection
+// holds idx (8 m bytes), sel (N bytes) and its counts (4 m bytes) on the device.
+int snap_save(fs2_handle *h, const int64_t *idx, int64_t m, void *buf, int64_t capacity, int64_t *size) {
+    hipStream_t s = h->stream;
+    const int c = h->cur;
+    Pool &p = h->pages, &r = h->records;
+    const MapRef map = h->map();
+    DevBuf didx, dsel, dcnt;
+    std::vector<int32_t> hc((size_t)m);
+    if (idx) {
+        std::vector<uint8_t> sel((size_t)h->n, 0);
+        const int64_t bad = snap_select_classes(idx, m, h->n, sel.data());
+        if (bad >= 0)
+            return set_err(&h->err, FS2_ERR_ARG, "fs2_snapshot_save_select: idx[%lld] = %lld is outside [0, %lld)",
+                           (long long)bad, (long long)idx[bad], (long long)h->n);
+        HIP_TRY(h, didx.alloc(sizeof(int64_t) * (size_t)m));
+        HIP_TRY(h, dsel.alloc((size_t)h->n));
+        HIP_TRY(h, dcnt.alloc(sizeof(int32_t) * (size_t)m));
+        if (int rc = snap_copy(h, didx.p, idx, 8 * m, hipMemcpyHostToDevice)) return rc;
+        if (int rc = snap_copy(h, dsel.p, sel.data(), h->n, hipMemcpyHostToDevice)) return rc;
+        HIP_TRY(h, launch_snap_scalars_sel(h->cnt[c], didx.as<int64_t>(), m, dcnt.as<int32_t>(), s));
+        if (int rc = snap_copy(h, hc.data(), dcnt.p, 4 * m, hipMemcpyDeviceToHost)) return rc;
+    } else {
+        HIP_TRY(h, copy_sync(h, hc.data(), h->cnt[c], sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost));
+    }
+    int32_t mx = 0;
+    for (int32_t v : hc) mx = std::max(mx, v);
+    const int R = (mx + kPageSlots - 1) / kPageSlots;
+    // the live pages and records, from the pools' marks at a fresh epoch: nothing is
+    // swept, so the free lists, their cursors and the next collection are as before
+    HIP_TRY(h, p.next_epoch(s));
+    if (idx) HIP_TRY(h, launch_snap_mark_sel(map, h->cnt[c], didx.as<int64_t>(), m, R, p.n, p.mark, p.epoch, s));
+    else HIP_TRY(h, launch_collect_mark(map, h->cnt[c], p.mark, p.epoch, nullptr, s));
+    HIP_TRY(h, r.next_epoch(s));
+    HIP_TRY(h, launch_mark_records(p.data, p.n, p.mark, p.epoch, r.n, r.mark, r.epoch, s));
+    DevBuf ptab, plist, rtab, rlist;
+    int64_t U = 0, C = 0;
+    if (int rc = snap_compact(h, p, ptab, plist, &U)) return rc;
+    if (int rc = snap_compact(h, r, rtab, rlist, &C)) return rc;
+
+    SnapHeader hd{};
+    std::memcpy(hd.magic, "FS2SNAP", 8);
+    hd.version = kSnapVersion;
+    hd.header_bytes = kSnapHeaderBytes;
+    hd.page_slots = kPageSlots;
+    hd.page_bytes = kPageBytes;
+    hd.rec_bytes = kRecBytes;
+    hd.cnt_upper = std::max(h->cnt_upper, mx);
+    hd.n = m;
+    hd.rows = R;
+    hd.pages = U;
+    hd.records = C;
+    hd.scan = h->scan;
+    hd.org = h->frame.org;
+    hd.cell = h->frame.cell;
+    hd.ext_seen = h->ext_seen;
+    hd.total = snap_layout(m, R, U, C, hd.sec);
+    *size = hd.total;
+    if (!buf) return FS2_OK;
+    if (capacity < hd.total)
+        return set_err(&h->err, FS2_ERR_ARG, "snapshot buffer too small (%lld < %lld)", (long long)capacity,
+                       (long long)hd.total);
+    HIP_TRY(h, copy_sync(h, &hd.slb, h->slb, sizeof(float), hipMemcpyDeviceToHost));
+    char *out = (char *)buf;
+    std::memcpy(out, &hd, sizeof hd);
+    for (int k = 0; k < kSnapSections; ++k) {        // pad bytes
+        const int64_t end = hd.sec[k][0] + hd.sec[k][1];
+        std::memset(out + end, 0, (size_t)((k + 1 < kSnapSections ? hd.sec[k + 1][0] : hd.total) - end));
+    }
+    const int64_t row_bytes = 4 * m;
+    const int64_t rows_per = std::max<int64_t>(1, kSnapPiece / row_bytes);
+    const int64_t pages_per = kSnapPiece / kPageBytes, recs_per = kSnapPiece / kRecBytes;
+    const int64_t vals_per = kSnapPiece / 8;         // (a selection's fp64 scalars)
+    const int64_t stage_bytes = std::max(std::max(std::max(std::min<int64_t>(rows_per, R) * row_bytes,
+                                                           std::min(pages_per, U) * kPageBytes),
+                                                  std::min(recs_per, C) * kRecBytes),
+                                         idx ? std::min(vals_per, m) * 8 : 0);
+    DevBuf stage;
+    HIP_TRY(h, stage.alloc((size_t)stage_bytes));
+    // scalars: straight from the current buffer set, a selection's gathered a piece at
+    // a time
+    {
+        char *q = out + hd.sec[kSnapScalars][0];
+        const double *src[4] = {h->x[c], h->y[c], h->yaw[c], h->w[c]};
+        for (int k = 0; k < 4; ++k) {
+            if (!idx) {
+                if (int rc = snap_copy(h, q + 8 * m * k, src[k], 8 * m, hipMemcpyDeviceToHost)) return rc;
+                continue;
+            }
+            for (int64_t k0 = 0; k0 < m; k0 += vals_per) {
+                const int64_t n = std::min(vals_per, m - k0);
+                HIP_TRY(h, launch_snap_scalars_sel(src[k], didx.as<int64_t>() + k0, n, stage.as<double>(), s));
+                HIP_TRY(h, copy_sync(h, q + 8 * (m * k + k0), stage.p, (size_t)(8 * n), hipMemcpyDeviceToHost));
+            }
+        }
+        std::memcpy(q + 32 * m, hc.data(), sizeof(int32_t) * (size_t)m);
+    }
+    // rows, pages and records through the staging buffer, a piece at a time
+    for (int64_t r0 = 0; r0 < R; r0 += rows_per) {
+        const int64_t k = std::min<int64_t>(rows_per, R - r0);
+        if (idx)
+            HIP_TRY(h, launch_snap_rows_sel(map, h->cnt[c], didx.as<int64_t>(), dsel.as<uint8_t>(), m,
+                                            ptab.as<uint32_t>(), p.n, (int)r0, (int)k, stage.as<uint32_t>(), s));
+        else
+            HIP_TRY(h, launch_snap_rows(map, h->cnt[c], ptab.as<uint32_t>(), p.n, (int)r0, (int)k,
+                                        stage.as<uint32_t>(), s));
+        HIP_TRY(h, copy_sync(h, out + hd.sec[kSnapRows][0] + r0 * row_bytes, stage.p, (size_t)(k * row_bytes),
+                             hipMemcpyDeviceToHost));
+    }
+    for (int64_t k0 = 0; k0 < U; k0 += pages_per) {
+        const int64_t k = std::min(pages_per, U - k0);
+        HIP_TRY(h, launch_snap_gather(p.data, plist.as<uint32_t>() + k0, k, kPageBytes / 16, rtab.as<uint32_t>(), r.n,
+                                      stage.p, s));
+        HIP_TRY(h, copy_sync(h, out + hd.sec[kSnapPages][0] + k0 * kPageBytes, stage.p, (size_t)(k * kPageBytes),
+                             hipMemcpyDeviceToHost));
+    }
+    for (int64_t k0 = 0; k0 < C; k0 += recs_per) {
+        const int64_t k = std::min(recs_per, C - k0);
+        HIP_TRY(h, launch_snap_gather(r.data, rlist.as<uint32_t>() + k0, k, kRecBytes / 16, nullptr, 0, stage.p, s));
+        HIP_TRY(h, copy_sync(h, out + hd.sec[kSnapRecords][0] + k0 * kRecBytes, stage.p, (size_t)(k * kRecBytes),
+                             hipMemcpyDeviceToHost));
+    }
+    return FS2_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3181,92 +3311,22 @@ int fs2_snapshot_check(const void *buf, int64_t size, fs2_snapshot_info *info) {
 int fs2_snapshot_save(fs2_handle *h, void *buf, int64_t capacity, int64_t *size) {
     if (int rc = snap_begin(h)) return rc;
     if (!size) return set_err(&h->err, FS2_ERR_ARG, "fs2_snapshot_save: size is null");
-    hipStream_t s = h->stream;
-    const int c = h->cur;
-    Pool &p = h->pages, &r = h->records;
-    const MapRef map = h->map();
-    // the live pages and records, from the pools' marks at a fresh epoch: nothing is
-    // swept, so the free lists, their cursors and the next collection are as before
-    HIP_TRY(h, p.next_epoch(s));
-    HIP_TRY(h, launch_collect_mark(map, h->cnt[c], p.mark, p.epoch, nullptr, s));
-    HIP_TRY(h, r.next_epoch(s));
-    HIP_TRY(h, launch_mark_records(p.data, p.n, p.mark, p.epoch, r.n, r.mark, r.epoch, s));
-    DevBuf ptab, plist, rtab, rlist;
-    int64_t U = 0, C = 0;
-    if (int rc = snap_compact(h, p, ptab, plist, &U)) return rc;
-    if (int rc = snap_compact(h, r, rtab, rlist, &C)) return rc;
-    std::vector<int32_t> hc((size_t)h->n);
-    HIP_TRY(h, copy_sync(h, hc.data(), h->cnt[c], sizeof(int32_t) * (size_t)h->n, hipMemcpyDeviceToHost));
-    int32_t mx = 0;
-    for (int32_t v : hc) mx = std::max(mx, v);
-    const int R = (mx + kPageSlots - 1) / kPageSlots;
+    return snap_save(h, nullptr, h->n, buf, capacity, size);
+}
 
-    SnapHeader hd{};
-    std::memcpy(hd.magic, "FS2SNAP", 8);
-    hd.version = kSnapVersion;
-    hd.header_bytes = kSnapHeaderBytes;
-    hd.page_slots = kPageSlots;
-    hd.page_bytes = kPageBytes;
-    hd.rec_bytes = kRecBytes;
-    hd.cnt_upper = std::max(h->cnt_upper, mx);
-    hd.n = h->n;
-    hd.rows = R;
-    hd.pages = U;
-    hd.records = C;
-    hd.scan = h->scan;
-    hd.org = h->frame.org;
-    hd.cell = h->frame.cell;
-    hd.ext_seen = h->ext_seen;
-    hd.total = snap_layout(h->n, R, U, C, hd.sec);
-    *size = hd.total;
-    if (!buf) return FS2_OK;
-    if (capacity < hd.total)
-        return set_err(&h->err, FS2_ERR_ARG, "snapshot buffer too small (%lld < %lld)", (long long)capacity,
-                       (long long)hd.total);
-    HIP_TRY(h, copy_sync(h, &hd.slb, h->slb, sizeof(float), hipMemcpyDeviceToHost));
-    char *out = (char *)buf;
-    std::memcpy(out, &hd, sizeof hd);
-    for (int k = 0; k < kSnapSections; ++k) {        // pad bytes
-        const int64_t end = hd.sec[k][0] + hd.sec[k][1];
-        std::memset(out + end, 0, (size_t)((k + 1 < kSnapSections ? hd.sec[k + 1][0] : hd.total) - end));
+int fs2_snapshot_save_select(fs2_handle *h, const int64_t *idx, int64_t m, void *buf, int64_t capacity,
+                             int64_t *size) {
+    if (!h) return set_err(nullptr, FS2_ERR_ARG, "null handle");
+    if (!idx) return set_err(&h->err, FS2_ERR_ARG, "fs2_snapshot_save_select: idx is null");
+    if (!size) return set_err(&h->err, FS2_ERR_ARG, "fs2_snapshot_save_select: size is null");
+    if (m < 1 || m > kSnapMaxParticles)
+        return set_err(&h->err, FS2_ERR_ARG, "fs2_snapshot_save_select: m = %lld is outside [1, 2^40]", (long long)m);
+    if (int rc = snap_begin(h)) return rc;
+    try {
+        return snap_save(h, idx, m, buf, capacity, size);
+    } catch (const std::bad_alloc &) {       // (the host copies of sel and the counts: m is the caller's)
+        return set_err(&h->err, FS2_ERR_OOM, "fs2_snapshot_save_select: out of host memory for m = %lld", (long long)m);
     }
-    // scalars, straight from the current buffer set
-    {
-        char *q = out + hd.sec[kSnapScalars][0];
-        const double *src[4] = {h->x[c], h->y[c], h->yaw[c], h->w[c]};
-        for (int k = 0; k < 4; ++k)
-            if (int rc = snap_copy(h, q + 8 * h->n * k, src[k], 8 * h->n, hipMemcpyDeviceToHost)) return rc;
-        std::memcpy(q + 32 * h->n, hc.data(), sizeof(int32_t) * (size_t)h->n);
-    }
-    // rows, pages and records through the staging buffer, a piece at a time
-    const int64_t row_bytes = 4 * h->n;
-    const int64_t rows_per = std::max<int64_t>(1, kSnapPiece / row_bytes);
-    const int64_t pages_per = kSnapPiece / kPageBytes, recs_per = kSnapPiece / kRecBytes;
-    const int64_t stage_bytes = std::max(std::max(std::min<int64_t>(rows_per, R) * row_bytes,
-                                                  std::min(pages_per, U) * kPageBytes),
-                                         std::min(recs_per, C) * kRecBytes);
-    DevBuf stage;
-    HIP_TRY(h, stage.alloc((size_t)stage_bytes));
-    for (int64_t r0 = 0; r0 < R; r0 += rows_per) {
-        const int64_t k = std::min<int64_t>(rows_per, R - r0);
-        HIP_TRY(h, launch_snap_rows(map, h->cnt[c], ptab.as<uint32_t>(), p.n, (int)r0, (int)k, stage.as<uint32_t>(), s));
-        HIP_TRY(h, copy_sync(h, out + hd.sec[kSnapRows][0] + r0 * row_bytes, stage.p, (size_t)(k * row_bytes),
-                             hipMemcpyDeviceToHost));
-    }
-    for (int64_t k0 = 0; k0 < U; k0 += pages_per) {
-        const int64_t k = std::min(pages_per, U - k0);
-        HIP_TRY(h, launch_snap_gather(p.data, plist.as<uint32_t>() + k0, k, kPageBytes / 16, rtab.as<uint32_t>(), r.n,
-                                      stage.p, s));
-        HIP_TRY(h, copy_sync(h, out + hd.sec[kSnapPages][0] + k0 * kPageBytes, stage.p, (size_t)(k * kPageBytes),
-                             hipMemcpyDeviceToHost));
-    }
-    for (int64_t k0 = 0; k0 < C; k0 += recs_per) {
-        const int64_t k = std::min(recs_per, C - k0);
-        HIP_TRY(h, launch_snap_gather(r.data, rlist.as<uint32_t>() + k0, k, kRecBytes / 16, nullptr, 0, stage.p, s));
-        HIP_TRY(h, copy_sync(h, out + hd.sec[kSnapRecords][0] + k0 * kRecBytes, stage.p, (size_t)(k * kRecBytes),
-                             hipMemcpyDeviceToHost));
-    }
-    return FS2_OK;
 }
 
 int fs2_snapshot_load(fs2_handle *h, const void *buf, int64_t size) {

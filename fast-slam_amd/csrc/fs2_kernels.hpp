@@ -784,6 +784,17 @@ hipError_t launch_snap_rows(MapRef map, const int32_t *cnt, const uint32_t *ptab
                             uint32_t *out, hipStream_t s);
 hipError_t launch_snap_gather(const char *pool, const uint32_t *ids, int64_t k, int L, const uint32_t *rtab,
                               int64_t nrecs, void *out, hipStream_t s);
+// Save of a selection idx[0 .. m) (device pointer, every idx[k] in [0, map.n); sel[i]:
+// 0, 1 or 2 = particle i taken never, once, more often): the pages of the selected maps
+// marked (R: rows of the longest selected map); src gathered through idx[0 .. k); the
+// rows with column k = particle idx[k], the owned bit kept where sel == 1.
+hipError_t launch_snap_mark_sel(MapRef map, const int32_t *cnt, const int64_t *idx, int64_t m, int R, int64_t npool,
+                                uint8_t *mark, uint8_t epoch, hipStream_t s);
+hipError_t launch_snap_scalars_sel(const double *src, const int64_t *idx, int64_t k, double *out, hipStream_t s);
+hipError_t launch_snap_scalars_sel(const int32_t *src, const int64_t *idx, int64_t k, int32_t *out, hipStream_t s);
+hipError_t launch_snap_rows_sel(MapRef map, const int32_t *cnt, const int64_t *idx, const uint8_t *sel, int64_t m,
+                                const uint32_t *ptab, int64_t npool, int r0, int nrows, uint32_t *out,
+                                hipStream_t s);
 // Restore: item j of `in` to pool id ids[j]; one pass (0, then 1) of snap_check_particles
 // over every particle (owners [U], shared [U], flags [2] zeroed by the caller: flags[0]
 // the first violated rule, flags[1] set when a map needs all R rows); then the installed

@@ -11,6 +11,13 @@
 //   k_snap_rows   the page table's rows, entries renumbered, the owned bit kept
 //   k_snap_gather pages (8 lanes x 16 B each, the record id renumbered in the lane that
 //                 holds it) and records (3 lanes x 16 B each), contiguous stores
+// A selection (fs2_snapshot_save_select: particles idx[0 .. m)) differs in what is
+// marked and in how the per-particle sections are read:
+//   k_snap_mark_sel     the page marks of the selected maps alone (m x R entries)
+//   k_snap_scalars_sel  x, y, yaw, w, cnt gathered through idx
+//   k_snap_rows_sel     the rows gathered through idx; the owned bit only where the
+//                       source particle was taken once
+// The record marks, the compaction and the gathers of pages and records are the same.
 //
 // Restore.  Pieces of the pages and records sections are scattered to the reserved
 // pool ids (k_snap_scatter), still with the snapshot's compact record ids; the rows
@@ -128,6 +135,89 @@ hipError_t launch_snap_rows(MapRef map, const int32_t *cnt, const uint32_t *ptab
     if (total > 0)
         hipLaunchKernelGGL(k_snap_rows, dim3(snap_grid(total)), dim3(kBlock), 0, s, map.pt, map.n, cnt, ptab, npool,
                            r0, nrows, out);
+    return hipGetLastError();
+}
+
+// ---- a selection: particles idx[0 .. m) of the handle (fs2_snapshot_save_select) ----
+
+// The page marks of the selected maps alone.  One lane per (block of 8 rows, k), k
+// fastest: the idx loads coalesce, and so do the table loads of a contiguous idx (a
+// slice).  The entries are loaded 8 at a time before the mark stores, which may alias
+// them (k_mark, fs2_pages.hip).  A source taken twice stores the same byte to the same
+// address twice.
+__global__ __launch_bounds__(kBlock) void k_snap_mark_sel(const MapRef map, const int32_t *cnt, const int64_t *idx,
+                                                          int64_t m, int nblk, int64_t npool, uint8_t *mark,
+                                                          uint8_t epoch) {
+    const int64_t total = (int64_t)nblk * m;
+    for (int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x; t < total; t += (int64_t)gridDim.x * kBlock) {
+        const int r0 = (int)(t / m) * 8;
+        const int64_t i = idx[t % m];
+        const int rows = (cnt[i] + kPageSlots - 1) / kPageSlots;
+        if (r0 >= rows) continue;
+        uint32_t e[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) e[u] = *pt_entry(map, min(r0 + u, rows - 1), i);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const uint32_t id = e[u] & kIdMask;
+            if (r0 + u < rows && (int64_t)id < npool) mark[id] = epoch;
+        }
+    }
+}
+
+hipError_t launch_snap_mark_sel(MapRef map, const int32_t *cnt, const int64_t *idx, int64_t m, int R, int64_t npool,
+                                uint8_t *mark, uint8_t epoch, hipStream_t s) {
+    const int nblk = (R + 7) / 8;
+    if (nblk > 0)
+        hipLaunchKernelGGL(k_snap_mark_sel, dim3(snap_grid(nblk * m)), dim3(kBlock), 0, s, map, cnt, idx, m, nblk,
+                           npool, mark, epoch);
+    return hipGetLastError();
+}
+
+// rows [r0, r0 + nrows) of the selection's page table: column k is particle idx[k]'s;
+// the owned bit survives only where that particle was taken once (sel == 1)
+__global__ __launch_bounds__(kBlock) void k_snap_rows_sel(const Desc *pt, int64_t n, const int32_t *cnt,
+                                                          const int64_t *idx, const uint8_t *sel, int64_t m,
+                                                          const uint32_t *ptab, int64_t npool, int r0, int nrows,
+                                                          uint32_t *out) {
+    const int64_t total = (int64_t)nrows * m;
+    for (int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x; t < total; t += (int64_t)gridDim.x * kBlock) {
+        const int r = r0 + (int)(t / m);
+        const int64_t i = idx[t % m];
+        uint32_t o = kSnapNone;
+        if (r < (cnt[i] + kPageSlots - 1) / kPageSlots) {
+            const uint32_t e = pt[(int64_t)r * n + i];
+            const uint32_t id = e & kIdMask;
+            if ((int64_t)id < npool) o = ptab[id] | (sel[i] == 1 ? e & kOwned : 0u);
+        }
+        out[t] = o;
+    }
+}
+
+hipError_t launch_snap_rows_sel(MapRef map, const int32_t *cnt, const int64_t *idx, const uint8_t *sel, int64_t m,
+                                const uint32_t *ptab, int64_t npool, int r0, int nrows, uint32_t *out,
+                                hipStream_t s) {
+    const int64_t total = (int64_t)nrows * m;
+    if (total > 0)
+        hipLaunchKernelGGL(k_snap_rows_sel, dim3(snap_grid(total)), dim3(kBlock), 0, s, map.pt, map.n, cnt, idx, sel,
+                           m, ptab, npool, r0, nrows, out);
+    return hipGetLastError();
+}
+
+// out[j] = src[idx[j]], j < k: a piece of x, y, yaw, w (fp64) or of cnt
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_snap_scalars_sel(const T *src, const int64_t *idx, int64_t k, T *out) {
+    for (int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x; t < k; t += (int64_t)gridDim.x * kBlock)
+        out[t] = src[idx[t]];
+}
+
+hipError_t launch_snap_scalars_sel(const double *src, const int64_t *idx, int64_t k, double *out, hipStream_t s) {
+    if (k > 0) hipLaunchKernelGGL(k_snap_scalars_sel<double>, dim3(snap_grid(k)), dim3(kBlock), 0, s, src, idx, k, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_snap_scalars_sel(const int32_t *src, const int64_t *idx, int64_t k, int32_t *out, hipStream_t s) {
+    if (k > 0) hipLaunchKernelGGL(k_snap_scalars_sel<int32_t>, dim3(snap_grid(k)), dim3(kBlock), 0, s, src, idx, k, out);
     return hipGetLastError();
 }
 

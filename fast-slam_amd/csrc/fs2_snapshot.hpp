@@ -25,6 +25,25 @@
 // map's end in a partly filled last page may keep a stale record alive).  The row
 // boxes are not stored: a restore rebuilds them from the pages.
 //
+// Selections (fs2_snapshot_save_select: particles idx[0 .. m) of a handle, repeats
+// allowed, m may exceed N).  The result is an ordinary snapshot of m particles: output
+// particle k carries x, y, yaw, w, cnt and the map of particle idx[k] verbatim (weights
+// are not renormalised); scan, org, cell, ext_seen, slb and cnt_upper are the handle's.
+//   - Liveness is over the selection: R = ceil(max selected cnt / 8) (0 when every
+//     selected map is empty), a page is live when a row below ceil(cnt / 8) of a
+//     selected particle names it, a record when a mirror of such a page names it.
+//     Compact ids are the rank among those live ids, so R, U, C are the selection's own.
+//   - An entry keeps its owned bit only if its source particle occurs exactly once in
+//     idx (snap_select_classes); otherwise the bit is cleared.  That is sufficient for
+//     the rule below: in the handle no other particle names an owned page, so in the
+//     selection only copies of the same particle could, and theirs are all cleared.
+//     The copies of a repeated particle share its pages un-owned and copy them at their
+//     first write, as resampled siblings do.
+//   - idx = 0 .. N - 1 gives the full save byte for byte: the same marks, every
+//     particle taken once.
+//   - Not promised: an un-owned entry whose sharers were not selected stays un-owned
+//     (one page copy more at its first write, nothing else).
+//
 // Valid (snap_check_header, then snap_check_particles passes 0 and 1):
 //   - the header is self-consistent: magic, version, header size, the layout constants,
 //     counts in range, the section table equal to snap_layout's, total == size;
@@ -52,6 +71,7 @@ constexpr uint32_t kSnapNone = 0xffffffffu;      // a row entry past the map, a 
 constexpr uint32_t kSnapOwned = 0x80000000u;     // == kOwned
 constexpr uint32_t kSnapSlotBits = 0xfffu;       // == kSlotBits
 constexpr int64_t kSnapMaxRows = 512;            // == kMaxRows
+constexpr int64_t kSnapMaxParticles = (int64_t)1 << 40;
 enum : int { kSnapScalars, kSnapRows, kSnapPages, kSnapRecords, kSnapSections };
 
 struct SnapHeader {
@@ -126,7 +146,7 @@ __host__ __device__ inline int snap_check_header(const SnapHeader &h, int64_t si
     if (h.version != kSnapVersion) return kSnapVersionBad;
     if (h.header_bytes != (uint32_t)kSnapHeaderBytes) return kSnapHeaderSize;
     if (h.page_slots != 8 || h.page_bytes != 128 || h.rec_bytes != 48) return kSnapConstants;
-    if (h.n < 1 || h.n > (int64_t)1 << 40 || h.rows < 0 || h.rows > kSnapMaxRows || h.pages < 0 ||
+    if (h.n < 1 || h.n > kSnapMaxParticles || h.rows < 0 || h.rows > kSnapMaxRows || h.pages < 0 ||
         h.pages > (int64_t)0x7fffffff || h.records < 0 || h.records > (int64_t)0xfffffffe ||
         h.pages > h.rows * h.n || h.records > 8 * h.pages || h.cnt_upper < 0 || h.cnt_upper > 8 * kSnapMaxRows)
         return kSnapCounts;
@@ -197,6 +217,18 @@ __host__ __device__ inline int snap_check_particles(const SnapView &v, int64_t i
     }
     if (pass == 0 && i0 == 0 && i1 == v.n && v.rows > 0 && !*full) return kSnapRowsExact;
     return kSnapOk;
+}
+
+// A selection's index list, in one pass on the host: sel[i] (n bytes, zero on entry)
+// becomes 0, 1 or 2 -- particle i taken never, once, more than once.  Returns the first
+// position k with idx[k] outside [0, n), or -1 when there is none.
+inline int64_t snap_select_classes(const int64_t *idx, int64_t m, int64_t n, uint8_t *sel) {
+    for (int64_t k = 0; k < m; ++k) {
+        const int64_t i = idx[k];
+        if (i < 0 || i >= n) return k;
+        if (sel[i] < 2) ++sel[i];
+    }
+    return -1;
 }
 
 }  // namespace fs2

@@ -206,6 +206,7 @@ SIGNATURES = [
     ("fs2_set_state", C.c_int, [_H, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int32,
                                 C.c_int32]),
     ("fs2_snapshot_save", C.c_int, [_H, _vp, C.c_int64, C.POINTER(C.c_int64)]),
+    ("fs2_snapshot_save_select", C.c_int, [_H, _vp, C.c_int64, _vp, C.c_int64, C.POINTER(C.c_int64)]),
     ("fs2_snapshot_load", C.c_int, [_H, _vp, C.c_int64]),
     ("fs2_snapshot_check", C.c_int, [_vp, C.c_int64, C.POINTER(fs2_snapshot_info)]),
     ("fs2_get_assoc", C.c_int, [_H, _ip, C.c_int64, _ip]),

@@ -297,19 +297,42 @@ class FastSLAM2:
         self._particles = None
 
     # ------------------------------------------------------------ snapshots
-    def snapshot(self) -> np.ndarray:
+    def snapshot(self, select=None) -> np.ndarray:
         """The filter as one uint8 array (fs2_snapshot_save): particles, maps and the scan
         counter in the device's own compact form -- every distinct page and record once, so
         maps that resampled siblings share are stored once -- for `restore` to resume the run
         bit for bit.  One sizing call, then one save into a single allocation.
 
+        select: an integer array-like of particle indices in [0, N) (negative ones are
+        refused, not wrapped; repeats allowed; it may be longer than N).  The result is
+        then the snapshot of those particles in that order (fs2_snapshot_save_select), for
+        a filter of len(select) particles to `restore`: a thinned filter, a slice, a
+        permutation.  Poses, weights and maps are copied verbatim and only the pages and
+        records they reach are stored; a particle taken more than once shares its pages
+        between the copies.  Weights are not renormalised: set_state(w=...) on the
+        restored filter sets others and leaves the maps alone.
+
         With rng="numpy" or rng="numpy-host" the generator's state belongs to the caller:
         keep np.random.get_state() next to the snapshot and np.random.set_state() it before
         resuming.  rng="device" draws from (seed, scan counter), which the snapshot holds."""
         size = C.c_int64()
-        nat.check(self._lib.fs2_snapshot_save(self._h, None, 0, C.byref(size)), self._h)
+        if select is None:
+            def save(addr, cap):
+                return self._lib.fs2_snapshot_save(self._h, addr, cap, C.byref(size))
+        else:
+            idx = np.asarray(select)
+            if idx.dtype.kind not in "iu":
+                raise TypeError(f"select must hold integers, not {idx.dtype}")
+            if idx.dtype.kind == "u" and idx.size and int(idx.max()) > np.iinfo(np.int64).max:
+                raise ValueError("select holds an index above the int64 range")
+            idx = np.ascontiguousarray(idx.reshape(-1), dtype=np.int64)
+
+            def save(addr, cap):
+                return self._lib.fs2_snapshot_save_select(self._h, idx.ctypes.data, idx.size, addr, cap,
+                                                          C.byref(size))
+        nat.check(save(None, 0), self._h)
         out = np.empty(size.value, dtype=np.uint8)
-        nat.check(self._lib.fs2_snapshot_save(self._h, out.ctypes.data, out.size, C.byref(size)), self._h)
+        nat.check(save(out.ctypes.data, out.size), self._h)
         return out
 
     def restore(self, buf) -> None:

@@ -337,6 +337,21 @@ typedef struct fs2_snapshot_info {
  * capacity < *size -> FS2_ERR_ARG, nothing written (as fs2_particles_json).
  * A save changes nothing a later scan or pool collection sees. */
 int fs2_snapshot_save(fs2_handle *h, void *buf, int64_t capacity, int64_t *size);
+/* A snapshot of particles idx[0 .. m) of this handle, in that order (host pointer;
+ * 0 <= idx[k] < N; repeats allowed; m >= 1, m may exceed N).  Sizing, capacity and
+ * preconditions as fs2_snapshot_save.  The result is a version-1 snapshot of m particles:
+ * fs2_snapshot_load into a handle of m particles and fs2_snapshot_check take it as any
+ * other.  Output particle k carries x, y, yaw, w, cnt and the map of particle idx[k]
+ * verbatim (weights are NOT renormalised: fs2_set_state with w alone on the restored
+ * handle sets others and leaves the maps as they are); scan, cnt_upper and the summary
+ * grid are the handle's.  Only pages and records the selection reaches are stored, each
+ * once.  An entry keeps its owned bit only if its particle occurs exactly once in idx:
+ * the copies of a repeated particle share its pages and copy them at their first write,
+ * as resampled siblings do.  idx = 0 .. N-1 gives fs2_snapshot_save's bytes.
+ * FS2_ERR_ARG: idx or size null, m < 1 or above 2^40, an idx[k] outside [0, N) (position
+ * and value in fs2_last_error); every error leaves the handle and buf untouched. */
+int fs2_snapshot_save_select(fs2_handle *h, const int64_t *idx, int64_t m,
+                             void *buf, int64_t capacity, int64_t *size);
 /* Replaces the handle's particles, maps and scan counter (with cnt_upper, the summary
  * grid and the mirror bound); the handle's own configuration (noise, gate, seed,
  * reduce mode) stays.  The snapshot is validated completely first; on any error the

@@ -29,6 +29,7 @@
 #include "fs2_kernels.hpp"
 #include "fs2_mtrng.hpp"
 #include "fs2_plan.hpp"
+#include "fs2_posterior.hpp"
 #include "fs2_repr.hpp"
 #include "fs2_snapshot.hpp"
 
@@ -644,6 +645,12 @@ struct fs2_handle {
     char *json_text = nullptr;
     int64_t *json_boff = nullptr;
     size_t json_text_cap = 0, json_boff_cap = 0;
+    // the posterior readout (fs2_pose_moments / fs2_pose_density): the block partials,
+    // the folded results and the grid with its outside counter, grown on demand and
+    // kept between calls
+    double *post_part = nullptr, *post_out = nullptr;
+    unsigned long long *post_grid = nullptr;
+    size_t post_part_cap = 0, post_out_cap = 0, post_grid_cap = 0;
 
     MapRef map() const {
         return MapRef{pages.data, pt[cur], std::max<int64_t>(n, 1), rows, records.data, frame, slb, row_boxes(cur),
@@ -1712,6 +1719,7 @@ static void free_handle(fs2_handle *h) {
     hipFree(h->part_maxcnt); hipFree(h->cbuf); hipFree(h->bsum);
     hipFree(h->stats_dev); hipFree(h->noise_dev); hipFree(h->u0_dev); hipFree(h->assoc_dev);
     hipFree(h->json_text); hipFree(h->json_boff);
+    hipFree(h->post_part); hipFree(h->post_out); hipFree(h->post_grid);
     if (h->post_host) hipHostFree(h->post_host);
     hipFree(h->plan);
     if (h->pub_stats) hipHostFree(h->pub_stats);
@@ -4522,6 +4530,12 @@ int fs2_plan_sends(const int32_t *mlo, const int32_t *mhi, const int32_t *cnt, i
     return FS2_OK;
 }
 
+int fs2_density_scale(double wmax, int64_t n, int32_t *e) {
+    if (!e || !density_scale(wmax, n, e))
+        return set_err(nullptr, FS2_ERR_ARG, "fs2_density_scale: wmax must be positive and finite, n >= 1");
+    return FS2_OK;
+}
+
 }  // extern "C"
 
 // ------------------------------------------------- viewer JSON (fs2_json.hip) ---
@@ -4638,6 +4652,28 @@ hipError_t json_grow_plain(void **p, size_t *cap, size_t need, const char *) {
     return e;
 }
 
+// A buffer a handle grows after its creation, allocated as fs2_create's: with FS2_GUARD
+// it is followed by the pattern (and sized exactly, so the pattern starts where the
+// contents end).
+hipError_t handle_grow(fs2_handle *h, void **p, size_t *cap, size_t need, const char *name) {
+    if (!h->guard) return json_grow_plain(p, cap, need, name);
+    if (need == *cap && *p) return hipSuccess;
+    for (size_t k = 0; k < h->guards.size(); ++k)
+        if (*p && h->guards[k].at == static_cast<char *>(*p) + *cap) {
+            h->guards.erase(h->guards.begin() + (ptrdiff_t)k);
+            break;
+        }
+    (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    hipError_t e = hipMalloc(p, need + kGuardBytes);
+    if (e == hipSuccess) e = hipMemset(static_cast<char *>(*p) + need, kGuardByte, kGuardBytes);
+    if (e != hipSuccess) return e;
+    *cap = need;
+    h->guards.push_back(fs2_handle::Guard{static_cast<char *>(*p) + need, name});
+    return hipSuccess;
+}
+
 }  // namespace
 
 extern "C" {
@@ -4716,26 +4752,7 @@ int fs2_particles_json(fs2_handle *h, int64_t first, int64_t count, int32_t dept
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     int rc = FS2_OK;
     if (json_empty(&h->err, count, buf, capacity, size, &rc)) return rc;
-    // the handle's buffers are allocated as fs2_create's: with FS2_GUARD each is
-    // followed by the pattern (and sized exactly, so the pattern starts where the text ends)
-    auto grow = [h](void **p, size_t *cap, size_t need, const char *name) -> hipError_t {
-        if (!h->guard) return json_grow_plain(p, cap, need, name);
-        if (need == *cap && *p) return hipSuccess;
-        for (size_t k = 0; k < h->guards.size(); ++k)
-            if (*p && h->guards[k].at == static_cast<char *>(*p) + *cap) {
-                h->guards.erase(h->guards.begin() + (ptrdiff_t)k);
-                break;
-            }
-        (void)hipFree(*p);
-        *p = nullptr;
-        *cap = 0;
-        hipError_t e = hipMalloc(p, need + kGuardBytes);
-        if (e == hipSuccess) e = hipMemset(static_cast<char *>(*p) + need, kGuardByte, kGuardBytes);
-        if (e != hipSuccess) return e;
-        *cap = need;
-        h->guards.push_back(fs2_handle::Guard{static_cast<char *>(*p) + need, name});
-        return hipSuccess;
-    };
+    auto grow = [h](void **p, size_t *cap, size_t need, const char *name) { return handle_grow(h, p, cap, need, name); };
     JsonBufs b{&h->json_text, &h->json_text_cap, &h->json_boff, &h->json_boff_cap, grow};
     const int c = h->cur;
     return json_emit(&h->err, h->cfg.device, b, h->x[c] + first, h->y[c] + first, h->yaw[c] + first, count, depth, buf,
@@ -4747,6 +4764,174 @@ int fs2_debug_json_times(int32_t enable, double ms[4]) {
     if (ms) {
         std::lock_guard<std::mutex> lk(g_json_ms_mu);
         std::memcpy(ms, g_json_ms, sizeof g_json_ms);
+    }
+    return FS2_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------- posterior readout (fs2_posterior.hip) ---
+// Moments and a density grid of the particle cloud from the current buffer set.  Both
+// only read x / y / yaw / w[cur]; what they write is the handle's readout scratch.
+
+namespace {
+
+// fs2_particles_json's prologue, for single-rank handles
+int post_begin(fs2_handle *h, const char *what) {
+    if (!h) return set_err(nullptr, FS2_ERR_ARG, "null handle");
+    if (h->pending.on) return set_err(&h->err, FS2_ERR_STATE, "a submitted scan is pending (fs2_iterate_wait first)");
+    if (h->tp || h->cfg.world_size > 1 || h->cfg.sharded_path)
+        return set_err(&h->err, FS2_ERR_STATE, "%s needs every particle on one rank (not the sharded path)", what);
+    if (h->n < 1) return set_err(&h->err, FS2_ERR_STATE, "%s: no particles", what);
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const int rcm = mt_finish(h);        // (as fs2_get_state)
+    h->mt.armed = false;
+    if (rcm) return rcm;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, handle_grow(h, (void **)&h->post_part, &h->post_part_cap,
+                           sizeof(double) * (size_t)kPostRowsMax * (size_t)post_blocks(h->n), "post_part"));
+    HIP_TRY(h, handle_grow(h, (void **)&h->post_out, &h->post_out_cap, sizeof(double) * kPostOut, "post_out"));
+    return FS2_OK;
+}
+
+// fs2_debug_posterior_times: device times of the last readout's two stages, when enabled
+std::atomic<int> g_post_timing{0};
+std::mutex g_post_ms_mu;
+double g_post_ms[2] = {};
+
+// Events around a readout's two stages on its stream: mark(0) / mark(1) around the
+// first, mark(2) / mark(3) around the second (a stage not run reads 0); done() after
+// the stream was synchronised.
+struct PostTimer {
+    hipEvent_t ev[4] = {};
+    bool marked[4] = {};
+    hipStream_t s;
+    bool on;
+    explicit PostTimer(hipStream_t st) : s(st), on(g_post_timing.load() != 0) {
+        if (on)
+            for (auto &e : ev) on = on && hipEventCreate(&e) == hipSuccess;
+    }
+    void mark(int k) {
+        if (on) marked[k] = hipEventRecord(ev[k], s) == hipSuccess;
+    }
+    void done() {
+        if (!on) return;
+        double ms[2] = {};
+        for (int k = 0; k < 2; ++k) {
+            float t = 0.0f;
+            if (marked[2 * k] && marked[2 * k + 1] &&
+                hipEventElapsedTime(&t, ev[2 * k], ev[2 * k + 1]) == hipSuccess)
+                ms[k] = t;
+        }
+        std::lock_guard<std::mutex> lk(g_post_ms_mu);
+        std::memcpy(g_post_ms, ms, sizeof ms);
+    }
+    ~PostTimer() {
+        for (auto &e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+int post_bad_weights(fs2_handle *h, const char *what, double bad, double total) {
+    if (bad != 0.0)
+        return set_err(&h->err, FS2_ERR_STATE, "%s: %.0f weights are negative or not finite", what, bad);
+    return set_err(&h->err, FS2_ERR_STATE, "%s: the weights sum to %g", what, total);
+}
+
+}  // namespace
+
+extern "C" {
+
+int fs2_pose_moments(fs2_handle *h, int32_t weighted, double mean[3], double cov[9], double sums[4], double bbox[4]) {
+    if (const int rc = post_begin(h, "fs2_pose_moments")) return rc;
+    const int c = h->cur;
+    const double *x = h->x[c], *y = h->y[c], *yaw = h->yaw[c], *w = h->w[c];
+    double o[kPostOut];
+    PostTimer tm(h->stream);
+    tm.mark(0);
+    HIP_TRY(h, launch_pose_first(x, y, yaw, w, h->n, weighted != 0, h->post_part, h->post_out, h->stream));
+    tm.mark(1);
+    HIP_TRY(h, copy_sync(h, o, h->post_out, sizeof o, hipMemcpyDeviceToHost));
+    const double W = o[kPmW];
+    if (weighted && (o[kPmBad] != 0.0 || !(W > 0.0) || !std::isfinite(W)))
+        return post_bad_weights(h, "fs2_pose_moments", o[kPmBad], W);
+    // the sums are about the pivot (particle 0's pose): shifted back here
+    const double *pivot = o + kPmRows;
+    const double mx = pivot[0] + o[kPmSx] / W, my = pivot[1] + o[kPmSy] / W;
+    const double myaw = wrap_pi(pivot[2] + std::atan2(o[kPmSs], o[kPmSc]));
+    double cv[kPcRows] = {};
+    if (cov) {
+        tm.mark(2);
+        HIP_TRY(h, launch_pose_second(x, y, yaw, w, h->n, weighted != 0, mx, my, myaw, h->post_part, h->post_out,
+                                      h->stream));
+        tm.mark(3);
+        HIP_TRY(h, copy_sync(h, cv, h->post_out, sizeof cv, hipMemcpyDeviceToHost));
+        const double xx = cv[kPcXX] / W, xy = cv[kPcXY] / W, xt = cv[kPcXT] / W, yy = cv[kPcYY] / W,
+                     yt = cv[kPcYT] / W, tt = cv[kPcTT] / W;
+        const double m[9] = {xx, xy, xt, xy, yy, yt, xt, yt, tt};
+        std::memcpy(cov, m, sizeof m);
+    }
+    tm.done();
+    if (mean) {
+        mean[0] = mx;
+        mean[1] = my;
+        mean[2] = myaw;
+    }
+    if (sums) {
+        sums[0] = W;
+        sums[1] = o[kPmW2];
+        sums[2] = std::hypot(o[kPmSs], o[kPmSc]) / W;
+        sums[3] = (double)h->n;
+    }
+    if (bbox) {
+        bbox[0] = o[kPmMinX];
+        bbox[1] = o[kPmMinY];
+        bbox[2] = o[kPmMaxX];
+        bbox[3] = o[kPmMaxY];
+    }
+    return FS2_OK;
+}
+
+int fs2_pose_density(fs2_handle *h, int32_t weighted, double x0, double y0, double cell, int32_t nx, int32_t ny,
+                     uint64_t *grid, int32_t *scale_exp, uint64_t *outside) {
+    if (!h) return set_err(nullptr, FS2_ERR_ARG, "null handle");
+    if (!grid || !(cell > 0.0) || !std::isfinite(cell) || nx < 1 || ny < 1 || (int64_t)nx * ny > kPdMaxCells)
+        return set_err(&h->err, FS2_ERR_ARG,
+                       "fs2_pose_density: bad arguments (a grid, a finite cell > 0, nx, ny >= 1, nx ny <= 2^24)");
+    if (const int rc = post_begin(h, "fs2_pose_density")) return rc;
+    const int c = h->cur;
+    int32_t e = 0;
+    PostTimer tm(h->stream);
+    if (weighted) {
+        double o[kPwRows];
+        tm.mark(0);
+        HIP_TRY(h, launch_weight_scan(h->w[c], h->n, h->post_part, h->post_out, h->stream));
+        tm.mark(1);
+        HIP_TRY(h, copy_sync(h, o, h->post_out, sizeof o, hipMemcpyDeviceToHost));
+        if (o[kPwBad] != 0.0 || !density_scale(o[kPwWmax], h->n, &e))
+            return post_bad_weights(h, "fs2_pose_density", o[kPwBad], o[kPwBad] != 0.0 ? 0.0 : o[kPwWmax]);
+    }
+    const size_t cells = (size_t)nx * (size_t)ny;
+    HIP_TRY(h, handle_grow(h, (void **)&h->post_grid, &h->post_grid_cap, sizeof(uint64_t) * (cells + 1), "post_grid"));
+    tm.mark(2);
+    HIP_TRY(h, hipMemsetAsync(h->post_grid, 0, sizeof(uint64_t) * (cells + 1), h->stream));
+    HIP_TRY(h, launch_pose_density(h->x[c], h->y[c], h->w[c], h->n, weighted != 0, x0, y0, cell, nx, ny, e,
+                                   h->post_grid, h->stream));
+    tm.mark(3);
+    uint64_t out = 0;
+    HIP_TRY(h, hipMemcpyAsync(grid, h->post_grid, sizeof(uint64_t) * cells, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, copy_sync(h, &out, h->post_grid + cells, sizeof out, hipMemcpyDeviceToHost));
+    tm.done();
+    if (scale_exp) *scale_exp = e;
+    if (outside) *outside = out;
+    return FS2_OK;
+}
+
+int fs2_debug_posterior_times(int32_t enable, double ms[2]) {
+    if (enable >= 0) g_post_timing.store(enable ? 1 : 0);
+    if (ms) {
+        std::lock_guard<std::mutex> lk(g_post_ms_mu);
+        std::memcpy(ms, g_post_ms, sizeof g_post_ms);
     }
     return FS2_OK;
 }

@@ -20,7 +20,9 @@ GPU (not numpy's stream; used by bench.py).
 from __future__ import annotations
 
 import ctypes as C
+import math
 from collections.abc import Sequence
+from typing import NamedTuple
 
 import numpy as np
 
@@ -42,6 +44,43 @@ _new_bytes.argtypes = [C.c_char_p, C.c_ssize_t]
 _bytes_addr = C.pythonapi.PyBytes_AsString
 _bytes_addr.restype = C.c_void_p
 _bytes_addr.argtypes = [C.py_object]
+
+
+class PoseMoments(NamedTuple):
+    """FastSLAM2.pose_moments' result."""
+    mean: np.ndarray            # (3,): x, y, circular mean of yaw
+    cov: np.ndarray             # (3, 3) weighted population covariance
+    weight_sum: float           # W
+    weight_sq_sum: float        # sum of w^2
+    resultant: float            # mean resultant length of the yaws
+    bbox: np.ndarray            # (4,): min x, min y, max x, max y
+
+
+def fit_density_window(bbox, shape, origin=None, cell=None):
+    """FastSLAM2.pose_density's window rule (documented there): (origin, cell) for a grid
+    of shape (ny, nx) over bbox = (xmin, ymin, xmax, ymax), given neither, or one, of them."""
+    ny, nx = shape
+    lo, hi, n = (float(bbox[0]), float(bbox[1])), (float(bbox[2]), float(bbox[3])), (nx, ny)
+    if not all(math.isfinite(v) for v in lo + hi):
+        raise ValueError(f"pose_density: cannot fit a window to the bounding box {lo + hi}")
+    fitted = origin is None
+
+    def snap(c):
+        return tuple(math.floor(lo[a] / c) * c if n[a] > 1 else lo[a] for a in range(2))
+
+    if cell is not None:
+        return snap(float(cell)), float(cell)
+    org = lo if fitted else (float(origin[0]), float(origin[1]))
+    c = max((hi[a] - org[a]) / (max(n[a] - 1, 1) if fitted else n[a]) for a in range(2))
+    if not c > 0.0:
+        c = 1.0
+    for _ in range(256):
+        if fitted:
+            org = snap(c)
+        if all(math.floor((hi[a] - org[a]) / c) <= n[a] - 1 for a in range(2)):
+            return org, c
+        c *= 1.0625
+    raise ValueError(f"pose_density: no cell covers the bounding box {lo + hi} in shape {shape}")
 
 
 class FastSLAM2:
@@ -391,6 +430,82 @@ class FastSLAM2:
                                                addr + len(head), n, C.byref(size)), self._h)
         C.memmove(addr + len(head) + n, tail, len(tail))
         return out
+
+    # ------------------------------------------------------ posterior readout
+    def _moments_raw(self, weighted, what, cov=True):
+        if not getattr(self, "_h", None):
+            raise nat.FS2Error(nat.FS2_ERR_ARG, f"{what}() on a closed FastSLAM2 handle")
+        mean, cv, sums, bbox = np.empty(3), (np.empty((3, 3)) if cov else None), np.empty(4), np.empty(4)
+        nat.check(self._lib.fs2_pose_moments(self._h, 1 if weighted else 0, nat.ptr(mean), nat.ptr(cv),
+                                             nat.ptr(sums), nat.ptr(bbox)), self._h)
+        return mean, cv, sums, bbox
+
+    def pose_moments(self, weighted: bool = True) -> "PoseMoments":
+        """Moments of the particle cloud, reduced on the device (fs2_pose_moments; DESIGN.md
+        §14): `mean` (x, y and the circular mean of yaw, in [-pi, pi)), `cov` the 3x3 weighted
+        population covariance of (x, y, yaw wrapped about its mean), `weight_sum` W,
+        `weight_sq_sum`, `resultant` (the mean resultant length of the yaws, 1 = all equal)
+        and `bbox` (min x, min y, max x, max y).
+
+        weighted=True weighs each particle by its weight as it stands and divides by W (the
+        weights need not sum to 1); weighted=False counts each particle once.  The reference
+        does not reset the weights at a resample, so right after a
+        resampling scan the weights still are those of the particles' sources while the
+        cloud itself already is the resampled posterior: there the unweighted form is the
+        cloud's own posterior.  FS2Error (FS2_ERR_STATE) for a negative or non-finite weight
+        or W = 0 when weighted, and on a sharded handle.  Two calls on the same state
+        return the same bits."""
+        mean, cov, sums, bbox = self._moments_raw(weighted, "pose_moments")
+        return PoseMoments(mean, cov, float(sums[0]), float(sums[1]), float(sums[2]), bbox)
+
+    def pose_density(self, shape, origin=None, cell=None, weighted: bool = True, raw: bool = False):
+        """A 2-D histogram of the particle positions, accumulated on the device in integers
+        (fs2_pose_density; exact, independent of summation order).  shape = (ny, nx); the
+        particle at (x, y) counts in grid[iy, ix], ix = floor((x - origin[0]) / cell),
+        iy = floor((y - origin[1]) / cell), when that lies in the grid; every other particle
+        (a non-finite pose too) counts in `outside`.  Amounts: 1 per particle when not
+        weighted, else q = rint(w 2^e) with the exponent e the library chooses from the
+        largest weight and the particle count (fs2_density_scale).
+
+        Returns (grid, outside, origin, cell): grid float64 [ny, nx], the counts times
+        2^-e (sums of weights up to the rounding of each q), outside likewise, origin a
+        tuple (x0, y0).  raw=True returns the uint64 counts and the int outside instead,
+        and appends e: (grid, outside, origin, cell, scale_exp).
+
+        The window.  With origin and cell both given it is used as it is.  Otherwise it is
+        fitted to pose_moments' bbox = (xmin, ymin, xmax, ymax), which must be finite:
+          * cell given, origin None: origin = (floor(xmin / cell) cell, floor(ymin / cell) cell)
+            (on an axis of one cell: the bbox minimum itself, see below).
+          * cell None: the spans are sx = xmax - x_lo, sy = ymax - y_lo with (x_lo, y_lo) the
+            given origin, or (xmin, ymin) when origin is None; the divisors are dx = nx,
+            dy = ny for a given origin and dx = max(nx - 1, 1), dy = max(ny - 1, 1) for a
+            fitted one (snapping the origin down can cost up to one cell);
+            cell = max(sx / dx, sy / dy), or 1.0 if that is not positive.  A fitted origin is
+            snapped down to a multiple of the cell as above, except on an axis of one cell,
+            where it is the bbox minimum itself (one cell at a multiple of its size cannot
+            cover a cloud that straddles one).  Then, while floor((xmax - x0) / cell) > nx - 1
+            or floor((ymax - y0) / cell) > ny - 1 (the device's own index arithmetic), cell
+            is multiplied by 1.0625 and a fitted origin snapped again.
+        With a fitted origin and cell no particle of a finite cloud is outside.
+        `fit_density_window` is this rule as a function."""
+        if not getattr(self, "_h", None):
+            raise nat.FS2Error(nat.FS2_ERR_ARG, "pose_density() on a closed FastSLAM2 handle")
+        ny, nx = (int(v) for v in shape)
+        if origin is None or cell is None:
+            if nx < 1 or ny < 1:
+                raise ValueError("pose_density: shape must be (ny >= 1, nx >= 1)")
+            origin, cell = fit_density_window(self._moments_raw(False, "pose_density", cov=False)[3], (ny, nx),
+                                              origin, cell)
+        x0, y0, cell = float(origin[0]), float(origin[1]), float(cell)
+        counts = np.empty((max(ny, 0), max(nx, 0)), dtype=np.uint64)
+        e, out = C.c_int32(), C.c_uint64()
+        nat.check(self._lib.fs2_pose_density(self._h, 1 if weighted else 0, x0, y0, cell, nx, ny,
+                                             nat.ptr(counts) if counts.size else None, C.byref(e), C.byref(out)),
+                  self._h)
+        if raw:
+            return counts, int(out.value), (x0, y0), cell, int(e.value)
+        return (np.ldexp(counts.astype(np.float64), -e.value), float(np.ldexp(float(out.value), -e.value)),
+                (x0, y0), cell)
 
     def cluster_landmarks(self, eps: float = 0.5, min_fraction: float = 0.7):
         """Centres [K][2] of DBSCAN over every particle's landmarks, on the device

@@ -481,6 +481,55 @@ int fs2_particles_json(fs2_handle *h, int64_t first, int64_t count, int32_t dept
  * the write pass, the download (the last two 0 for a sizing call). */
 int fs2_debug_json_times(int32_t enable, double ms[4]);
 
+/* -------------------------------------------------------- posterior readout ---- */
+
+/* Summaries of the particle cloud from the device-resident poses and weights (the
+ * current buffer set), beside the reference's only one, the heaviest particle's pose
+ * (__estimate_robot_position, fast_slam_2.py:201-210).  DESIGN.md §14.
+ * Preconditions as fs2_particles_json: FS2_ERR_STATE while scans are outstanding; a
+ * pending deferred draw is ended first; the handle's stream is synchronised.  Handles
+ * that run the sharded path (world_size > 1 or sharded_path) return FS2_ERR_STATE.
+ * Neither call changes filter state: a later scan is bit for bit the scan without it.
+ *
+ * Weights: w_i is the particle's weight if `weighted`, else 1; W = sum w_i.  The weights
+ * are used as they stand (after a resampling scan the reference does not reset them, so
+ * they do not sum to 1; right after a resample the unweighted form is the cloud's own
+ * posterior).  With `weighted`, a negative or non-finite weight, or a W that is 0 or not
+ * finite, is FS2_ERR_STATE and nothing is written; without it the weights are not read.
+ *
+ * fs2_pose_moments:
+ *   mean  = (sum w x / W, sum w y / W, circular mean of yaw: the angle of
+ *           (sum w cos yaw, sum w sin yaw), in [-pi, pi));
+ *   cov   = row-major 3x3 weighted population covariance sum w d d^T / W of
+ *           d = (x - mean_x, y - mean_y, wrap(yaw - mean_yaw)), wrap into [-pi, pi),
+ *           from a second pass about the mean (symmetric by construction);
+ *   sums  = {W, sum w^2, R, n}: R = hypot(sum w sin yaw, sum w cos yaw) / W the mean
+ *           resultant length, n the particle count;
+ *   bbox  = {min x, min y, max x, max y} under fmin / fmax.
+ * Any output pointer may be NULL.  No floating-point atomics, and reductions whose shape
+ * depends on the particle count alone: the same state gives the same bits. */
+int fs2_pose_moments(fs2_handle *h, int32_t weighted, double mean[3], double cov[9], double sums[4],
+                     double bbox[4]);
+
+/* A 2-D histogram of the cloud, exact and independent of summation order (integer
+ * amounts).  Particle i falls in cell (ix, iy) = (floor((x_i - x0) / cell),
+ * floor((y_i - y0) / cell)) in IEEE fp64 and counts in grid[iy][ix] when 0 <= ix < nx
+ * and 0 <= iy < ny; otherwise (a non-finite pose too) its amount goes to *outside.
+ * Amounts: 1 without `weighted` (*scale_exp = 0); else q_i = rint(w_i 2^e), round half
+ * to even, e = *scale_exp as fs2_density_scale gives it for the largest weight and the
+ * particle count, so the grid holds the weights' sums times 2^e and the total stays
+ * below 2^63.  grid: host, [ny][nx]; scale_exp, outside: nullable.
+ * FS2_ERR_ARG: cell not finite or <= 0, nx or ny < 1, nx ny > 2^24, grid NULL. */
+int fs2_pose_density(fs2_handle *h, int32_t weighted, double x0, double y0, double cell,
+                     int32_t nx, int32_t ny, uint64_t *grid, int32_t *scale_exp, uint64_t *outside);
+
+/* Measurement hook (scripts/posterior_probe.py): enable = 1 / 0 turns HIP-event timing of
+ * the two entry points above on / off (process-wide; -1 leaves it); ms (nullable) receives
+ * the last timed call's device times: moments -- the first pass, the second pass;
+ * density -- the weight pass (0 without `weighted`), then zeroing the grid and the
+ * histogram. */
+int fs2_debug_posterior_times(int32_t enable, double ms[2]);
+
 /* Test hooks of the device generator that replaces the reference's
  * np.random draws when rng="device" (fast_slam_2.py:79,81 motion noise, :183
  * resample start): Philox4x32-10 (Salmon et al., Random123) and the motion
@@ -607,6 +656,13 @@ int fs2_plan_ranges(const double *c, int64_t n, int64_t first_global, int64_t N,
                     int32_t *mlo, int32_t *mhi);
 int fs2_plan_sends(const int32_t *mlo, const int32_t *mhi, const int32_t *cnt, int64_t n, int64_t N,
                    int32_t world, int32_t rank, int64_t *run, int64_t *K, int64_t *S);
+
+/* The exponent of fs2_pose_density's weighted amounts, on the host (no device needed):
+ * with frexp(wmax) = m 2^ex, m in [0.5, 1), *e = B - ex, B = min(52, 62 -
+ * ceil(log2(max(n, 2)))).  Then rint(wmax 2^e) is in [2^(B-1), 2^B] and n amounts stay
+ * below 2^63.  *e can exceed 1023 (a subnormal wmax): ldexp(w, e) is still exact, and
+ * nothing is clamped.  FS2_ERR_ARG: wmax not positive and finite, n < 1, e NULL. */
+int fs2_density_scale(double wmax, int64_t n, int32_t *e);
 
 #ifdef __cplusplus
 }

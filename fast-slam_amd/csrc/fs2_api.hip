@@ -29,6 +29,7 @@
 #include "fs2_kernels.hpp"
 #include "fs2_mtrng.hpp"
 #include "fs2_plan.hpp"
+#include "fs2_mapreadout.hpp"
 #include "fs2_posterior.hpp"
 #include "fs2_repr.hpp"
 #include "fs2_snapshot.hpp"
@@ -651,6 +652,13 @@ struct fs2_handle {
     double *post_part = nullptr, *post_out = nullptr;
     unsigned long long *post_grid = nullptr;
     size_t post_part_cap = 0, post_out_cap = 0, post_grid_cap = 0;
+    // the map readout (fs2_map_summary / fs2_map_density): the per-page tally (sized from
+    // the page pool at the time of the call), the counts and folded box, the summary
+    // pass's partials and the grid, grown on demand and kept between calls
+    char *map_scr = nullptr, *map_out = nullptr;
+    double *map_part = nullptr;
+    unsigned long long *map_grid = nullptr;
+    size_t map_scr_cap = 0, map_out_cap = 0, map_part_cap = 0, map_grid_cap = 0;
 
     MapRef map() const {
         return MapRef{pages.data, pt[cur], std::max<int64_t>(n, 1), rows, records.data, frame, slb, row_boxes(cur),
@@ -1720,6 +1728,7 @@ static void free_handle(fs2_handle *h) {
     hipFree(h->stats_dev); hipFree(h->noise_dev); hipFree(h->u0_dev); hipFree(h->assoc_dev);
     hipFree(h->json_text); hipFree(h->json_boff);
     hipFree(h->post_part); hipFree(h->post_out); hipFree(h->post_grid);
+    hipFree(h->map_scr); hipFree(h->map_out); hipFree(h->map_part); hipFree(h->map_grid);
     if (h->post_host) hipHostFree(h->post_host);
     hipFree(h->plan);
     if (h->pub_stats) hipHostFree(h->pub_stats);
@@ -4794,20 +4803,33 @@ int post_begin(fs2_handle *h, const char *what) {
     return FS2_OK;
 }
 
-// fs2_debug_posterior_times: device times of the last readout's two stages, when enabled
-std::atomic<int> g_post_timing{0};
-std::mutex g_post_ms_mu;
-double g_post_ms[2] = {};
+// Device times of a readout's stages, kept for a debug entry point (fs2_debug_posterior_times,
+// fs2_debug_map_times): the process-wide switch and the last timed call's figures.
+template <int STAGES>
+struct StageTimes {
+    std::atomic<int> on{0};
+    std::mutex mu;
+    double ms[STAGES] = {};
+    int debug(int32_t enable, double *out) {
+        if (enable >= 0) on.store(enable ? 1 : 0);
+        if (out) {
+            std::lock_guard<std::mutex> lk(mu);
+            std::memcpy(out, ms, sizeof ms);
+        }
+        return FS2_OK;
+    }
+};
 
-// Events around a readout's two stages on its stream: mark(0) / mark(1) around the
-// first, mark(2) / mark(3) around the second (a stage not run reads 0); done() after
-// the stream was synchronised.
-struct PostTimer {
-    hipEvent_t ev[4] = {};
-    bool marked[4] = {};
+// Events around a readout's stages on its stream: mark(2 k) / mark(2 k + 1) around stage k
+// (a stage not run reads 0); done() after the stream was synchronised.
+template <int STAGES>
+struct StageTimer {
+    hipEvent_t ev[2 * STAGES] = {};
+    bool marked[2 * STAGES] = {};
     hipStream_t s;
+    StageTimes<STAGES> &g;
     bool on;
-    explicit PostTimer(hipStream_t st) : s(st), on(g_post_timing.load() != 0) {
+    StageTimer(hipStream_t st, StageTimes<STAGES> &times) : s(st), g(times), on(times.on.load() != 0) {
         if (on)
             for (auto &e : ev) on = on && hipEventCreate(&e) == hipSuccess;
     }
@@ -4816,20 +4838,26 @@ struct PostTimer {
     }
     void done() {
         if (!on) return;
-        double ms[2] = {};
-        for (int k = 0; k < 2; ++k) {
+        double ms[STAGES] = {};
+        for (int k = 0; k < STAGES; ++k) {
             float t = 0.0f;
             if (marked[2 * k] && marked[2 * k + 1] &&
                 hipEventElapsedTime(&t, ev[2 * k], ev[2 * k + 1]) == hipSuccess)
                 ms[k] = t;
         }
-        std::lock_guard<std::mutex> lk(g_post_ms_mu);
-        std::memcpy(g_post_ms, ms, sizeof ms);
+        std::lock_guard<std::mutex> lk(g.mu);
+        std::memcpy(g.ms, ms, sizeof ms);
     }
-    ~PostTimer() {
+    ~StageTimer() {
         for (auto &e : ev)
             if (e) (void)hipEventDestroy(e);
     }
+};
+
+// the posterior readout's two stages
+StageTimes<2> g_post_times;
+struct PostTimer : StageTimer<2> {
+    explicit PostTimer(hipStream_t st) : StageTimer<2>(st, g_post_times) {}
 };
 
 int post_bad_weights(fs2_handle *h, const char *what, double bad, double total) {
@@ -4927,13 +4955,144 @@ int fs2_pose_density(fs2_handle *h, int32_t weighted, double x0, double y0, doub
     return FS2_OK;
 }
 
-int fs2_debug_posterior_times(int32_t enable, double ms[2]) {
-    if (enable >= 0) g_post_timing.store(enable ? 1 : 0);
-    if (ms) {
-        std::lock_guard<std::mutex> lk(g_post_ms_mu);
-        std::memcpy(ms, g_post_ms, sizeof g_post_ms);
+int fs2_debug_posterior_times(int32_t enable, double ms[2]) { return g_post_times.debug(enable, ms); }
+
+}  // extern "C"
+
+// ------------------------------------------------- map readout (fs2_mapreadout.hip) ---
+// The counts, the bounding box and a density grid of every live landmark, from the
+// current page table and the pools.  Both only read cnt / w / pt[cur], the pages and the
+// records; what they write is the handle's readout scratch.
+
+namespace {
+
+// the map readout's three stages (fs2_debug_map_times)
+StageTimes<3> g_map_times;
+struct MapTimer : StageTimer<3> {
+    explicit MapTimer(hipStream_t st) : StageTimer<3>(st, g_map_times) {}
+};
+
+// map_out: kMcCells counts, then the folded rows of the summary pass
+constexpr size_t kMapOutBytes = sizeof(unsigned long long) * kMcCells + sizeof(double) * kMeRows;
+
+// The first two stages of both calls, after post_begin: the counts of cnt (and the
+// weights' scan), then the tally of the pool's pages.  counts: {T, R, max cnt}.
+int map_tally(fs2_handle *h, const char *what, bool weighted, MapTimer &tm, unsigned long long counts[kMcCells],
+              int32_t *e, MapTally *tl) {
+    const int c = h->cur;
+    const int64_t npool = h->pages.n;
+    HIP_TRY(h, handle_grow(h, (void **)&h->map_out, &h->map_out_cap, kMapOutBytes, "map_out"));
+    HIP_TRY(h, handle_grow(h, (void **)&h->map_scr, &h->map_scr_cap,
+                           kMrPageBytes * (size_t)std::max<int64_t>(npool, 1), "map_scr"));
+    unsigned long long *dcounts = reinterpret_cast<unsigned long long *>(h->map_out);
+    tm.mark(0);
+    HIP_TRY(h, hipMemsetAsync(dcounts, 0, sizeof(unsigned long long) * kMcCells, h->stream));
+    HIP_TRY(h, launch_map_counts(h->cnt[c], h->n, dcounts, h->stream));
+    if (weighted) HIP_TRY(h, launch_weight_scan(h->w[c], h->n, h->post_part, h->post_out, h->stream));
+    tm.mark(1);
+    double o[kPwRows] = {};
+    if (weighted) HIP_TRY(h, hipMemcpyAsync(o, h->post_out, sizeof o, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, copy_sync(h, counts, dcounts, sizeof(unsigned long long) * kMcCells, hipMemcpyDeviceToHost));
+    *e = 0;
+    if (weighted && (o[kPwBad] != 0.0 || !density_scale(o[kPwWmax], std::max<int64_t>((int64_t)counts[kMcT], 1), e)))
+        return post_bad_weights(h, what, o[kPwBad], o[kPwBad] != 0.0 ? 0.0 : o[kPwWmax]);
+    *tl = map_tally_views(h->map_scr, std::max<int64_t>(npool, 1));
+    tl->bad = dcounts + kMcBad;
+    // rows some map reaches; every map's live entries lie in the rows allocated
+    const int32_t rows = (int32_t)std::min<int64_t>(((int64_t)counts[kMcMax] + kPageSlots - 1) / kPageSlots, h->rows);
+    tm.mark(2);
+    HIP_TRY(h, hipMemsetAsync(h->map_scr, 0, kMrPageBytes * (size_t)std::max<int64_t>(npool, 1), h->stream));
+    HIP_TRY(h, launch_map_tally(h->map(), h->cnt[c], weighted ? h->w[c] : nullptr, h->n, rows, *e, npool, *tl,
+                                h->stream));
+    tm.mark(3);
+    return FS2_OK;
+}
+
+// After a call's last pass and before anything is written: the kMcBad cell's value (read
+// with map_bad_async before the call's last synchronising copy).  A live entry
+// or mirror that names a page or record past the pools was left out of the sums, so the
+// call fails instead of returning a quietly short result.
+int map_check_ids(fs2_handle *h, const char *what, unsigned long long bad) {
+    if (bad)
+        return set_err(&h->err, FS2_ERR_STATE, "%s: %llu live page-table entries or mirrors name a page or record "
+                       "past the pools (corrupted maps)", what, bad);
+    return FS2_OK;
+}
+
+hipError_t map_bad_async(fs2_handle *h, unsigned long long *bad) {
+    return hipMemcpyAsync(bad, reinterpret_cast<unsigned long long *>(h->map_out) + kMcBad, sizeof *bad,
+                          hipMemcpyDeviceToHost, h->stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int fs2_map_summary(fs2_handle *h, double bbox[4], int64_t counts[4]) {
+    if (const int rc = post_begin(h, "fs2_map_summary")) return rc;
+    MapTimer tm(h->stream);
+    unsigned long long cn[kMcCells];
+    int32_t e = 0;
+    MapTally tl{};
+    if (const int rc = map_tally(h, "fs2_map_summary", false, tm, cn, &e, &tl)) return rc;
+    HIP_TRY(h, handle_grow(h, (void **)&h->map_part, &h->map_part_cap, sizeof(double) * kMeRows * kMrGrid, "map_part"));
+    double *dout = reinterpret_cast<double *>(h->map_out + sizeof(unsigned long long) * kMcCells);
+    tm.mark(4);
+    HIP_TRY(h, launch_map_extent(h->pages.data, h->records.data, h->pages.n, h->records.n, tl, h->map_part, dout,
+                                 h->stream));
+    tm.mark(5);
+    double o[kMeRows];
+    unsigned long long bad = 0;
+    HIP_TRY(h, map_bad_async(h, &bad));
+    HIP_TRY(h, copy_sync(h, o, dout, sizeof o, hipMemcpyDeviceToHost));
+    tm.done();
+    if (const int rc = map_check_ids(h, "fs2_map_summary", bad)) return rc;
+    if (counts) {
+        counts[0] = (int64_t)cn[kMcT];
+        counts[1] = (int64_t)cn[kMcR];
+        counts[2] = (int64_t)o[kMeU];
+        counts[3] = (int64_t)cn[kMcMax];
+    }
+    if (bbox) {
+        bbox[0] = o[kMeMinX];
+        bbox[1] = o[kMeMinY];
+        bbox[2] = o[kMeMaxX];
+        bbox[3] = o[kMeMaxY];
     }
     return FS2_OK;
 }
+
+int fs2_map_density(fs2_handle *h, int32_t weighted, double x0, double y0, double cell, int32_t nx, int32_t ny,
+                    uint64_t *grid, int32_t *scale_exp, uint64_t *outside) {
+    if (!h) return set_err(nullptr, FS2_ERR_ARG, "null handle");
+    if (!grid || !(cell > 0.0) || !std::isfinite(cell) || nx < 1 || ny < 1 || (int64_t)nx * ny > kPdMaxCells)
+        return set_err(&h->err, FS2_ERR_ARG,
+                       "fs2_map_density: bad arguments (a grid, a finite cell > 0, nx, ny >= 1, nx ny <= 2^24)");
+    if (const int rc = post_begin(h, "fs2_map_density")) return rc;
+    MapTimer tm(h->stream);
+    unsigned long long cn[kMcCells];
+    int32_t e = 0;
+    MapTally tl{};
+    if (const int rc = map_tally(h, "fs2_map_density", weighted != 0, tm, cn, &e, &tl)) return rc;
+    const size_t cells = (size_t)nx * (size_t)ny;
+    HIP_TRY(h, handle_grow(h, (void **)&h->map_grid, &h->map_grid_cap, sizeof(uint64_t) * (cells + 1), "map_grid"));
+    tm.mark(4);
+    HIP_TRY(h, hipMemsetAsync(h->map_grid, 0, sizeof(uint64_t) * (cells + 1), h->stream));
+    HIP_TRY(h, launch_map_bin(h->pages.data, h->records.data, h->pages.n, h->records.n, tl, x0, y0, cell, nx, ny,
+                              h->map_grid, h->stream));
+    tm.mark(5);
+    uint64_t out = 0;
+    unsigned long long bad = 0;
+    HIP_TRY(h, map_bad_async(h, &bad));
+    HIP_TRY(h, copy_sync(h, &out, h->map_grid + cells, sizeof out, hipMemcpyDeviceToHost));
+    tm.done();
+    if (const int rc = map_check_ids(h, "fs2_map_density", bad)) return rc;
+    HIP_TRY(h, copy_sync(h, grid, h->map_grid, sizeof(uint64_t) * cells, hipMemcpyDeviceToHost));
+    if (scale_exp) *scale_exp = e;
+    if (outside) *outside = out;
+    return FS2_OK;
+}
+
+int fs2_debug_map_times(int32_t enable, double ms[3]) { return g_map_times.debug(enable, ms); }
 
 }  // extern "C"

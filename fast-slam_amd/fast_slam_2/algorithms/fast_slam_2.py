@@ -56,6 +56,15 @@ class PoseMoments(NamedTuple):
     bbox: np.ndarray            # (4,): min x, min y, max x, max y
 
 
+class MapSummary(NamedTuple):
+    """FastSLAM2.map_summary's result."""
+    landmarks: int              # T: sum of the particles' landmark counts
+    page_refs: int              # R: live page-table entries
+    pages: int                  # U: distinct pages they name
+    max_count: int              # largest landmark count of a particle
+    bbox: np.ndarray            # (4,): min x, min y, max x, max y of the landmark means
+
+
 def fit_density_window(bbox, shape, origin=None, cell=None):
     """FastSLAM2.pose_density's window rule (documented there): (origin, cell) for a grid
     of shape (ny, nx) over bbox = (xmin, ymin, xmax, ymax), given neither, or one, of them."""
@@ -501,6 +510,57 @@ class FastSLAM2:
         e, out = C.c_int32(), C.c_uint64()
         nat.check(self._lib.fs2_pose_density(self._h, 1 if weighted else 0, x0, y0, cell, nx, ny,
                                              nat.ptr(counts) if counts.size else None, C.byref(e), C.byref(out)),
+                  self._h)
+        if raw:
+            return counts, int(out.value), (x0, y0), cell, int(e.value)
+        return (np.ldexp(counts.astype(np.float64), -e.value), float(np.ldexp(float(out.value), -e.value)),
+                (x0, y0), cell)
+
+    # ------------------------------------------------------------ map readout
+    def map_summary(self) -> "MapSummary":
+        """Counts and bounding box of the map posterior -- every live landmark of every
+        particle -- from the page pool on the device (fs2_map_summary), without
+        forming a dense map: `landmarks` T = sum of the particles' landmark counts,
+        `page_refs` R = the live page-table entries (sum of ceil(count / 8)), `pages` U = the
+        distinct pages they name (U / R is the share of the maps the particles do not have in
+        common: 1 with nothing shared, small after resamples), `max_count`, and `bbox` (min x,
+        min y, max x, max y of the landmarks' fp64 means; (inf, inf, -inf, -inf) when there is
+        no landmark).  FS2Error (FS2_ERR_STATE) on a sharded handle and while a scan is
+        pending."""
+        if not getattr(self, "_h", None):
+            raise nat.FS2Error(nat.FS2_ERR_ARG, "map_summary() on a closed FastSLAM2 handle")
+        bbox, counts = np.empty(4), np.empty(4, dtype=np.int64)
+        nat.check(self._lib.fs2_map_summary(self._h, nat.ptr(bbox), nat.ptr(counts)), self._h)
+        return MapSummary(int(counts[0]), int(counts[1]), int(counts[2]), int(counts[3]), bbox)
+
+    def map_density(self, shape, origin=None, cell=None, weighted: bool = True, raw: bool = False):
+        """A 2-D histogram of every live landmark of every particle, accumulated on the device
+        in integers (fs2_map_density; exact, independent of summation order).
+        A landmark of particle i with fp64 mean (mx, my) counts in grid[iy, ix] by
+        pose_density's rule and adds the particle's amount: 1 when not weighted, else
+        q_i = rint(w_i 2^e), e chosen from the largest weight and the landmark total
+        (fs2_density_scale(wmax, max(T, 1))).  Each distinct page of the pool is opened once,
+        however many particles share it.
+
+        shape, origin, cell, raw and the return forms are pose_density's: (grid, outside,
+        origin, cell), or with raw=True the uint64 counts, the int outside and scale_exp
+        appended.  Without origin or cell the window is fitted to map_summary().bbox by
+        `fit_density_window`; with no landmark at all that is a ValueError."""
+        if not getattr(self, "_h", None):
+            raise nat.FS2Error(nat.FS2_ERR_ARG, "map_density() on a closed FastSLAM2 handle")
+        ny, nx = (int(v) for v in shape)
+        if origin is None or cell is None:
+            if nx < 1 or ny < 1:
+                raise ValueError("map_density: shape must be (ny >= 1, nx >= 1)")
+            ms = self.map_summary()
+            if ms.landmarks == 0:
+                raise ValueError("map_density: no landmark to fit a window to (give origin and cell)")
+            origin, cell = fit_density_window(ms.bbox, (ny, nx), origin, cell)
+        x0, y0, cell = float(origin[0]), float(origin[1]), float(cell)
+        counts = np.empty((max(ny, 0), max(nx, 0)), dtype=np.uint64)
+        e, out = C.c_int32(), C.c_uint64()
+        nat.check(self._lib.fs2_map_density(self._h, 1 if weighted else 0, x0, y0, cell, nx, ny,
+                                            nat.ptr(counts) if counts.size else None, C.byref(e), C.byref(out)),
                   self._h)
         if raw:
             return counts, int(out.value), (x0, y0), cell, int(e.value)

@@ -530,6 +530,45 @@ int fs2_pose_density(fs2_handle *h, int32_t weighted, double x0, double y0, doub
  * histogram. */
 int fs2_debug_posterior_times(int32_t enable, double ms[2]);
 
+/* -------------------------------------------------------------- map readout ---- */
+
+/* Summaries of the map posterior -- every live landmark (i, j), j < cnt_i, of every
+ * particle i -- from the page pool as it stands (the current buffer set's page table).
+ * DESIGN.md §15.  Resampled particles share pages, and the readout opens each distinct
+ * page once, weighted by the particles that refer to it; no dense map is formed.
+ * Preconditions, the sharded path and the weights exactly as the posterior readout
+ * above.  Neither call changes filter state, pools, boxes or free lists.  A live
+ * page-table entry or mirror that names a page or record past the pools (corrupted maps)
+ * is not followed: the call returns FS2_ERR_STATE and writes nothing.
+ *
+ * fs2_map_summary:
+ *   counts = {T, R, U, max_cnt}: T = sum cnt_i (live landmarks), R = sum ceil(cnt_i / 8)
+ *            (live page-table entries), U = distinct pages those entries name (U / R
+ *            measures how much of the maps the particles share), max_cnt = max cnt_i;
+ *   bbox   = {min x, min y, max x, max y} of the fp64 means of all live landmarks under
+ *            fmin / fmax (+inf, +inf, -inf, -inf when T = 0).
+ * Either pointer may be NULL. */
+int fs2_map_summary(fs2_handle *h, double bbox[4], int64_t counts[4]);
+
+/* A 2-D histogram of every live landmark of every particle, exact and independent of
+ * summation order.  Landmark (i, j) with fp64 record mean (mx, my) -- never the fp32 gate
+ * mirror -- falls in (floor((mx - x0) / cell), floor((my - y0) / cell)), fs2_pose_density's
+ * rule, outside and non-finite included, and adds particle i's amount q_i: 1 without
+ * `weighted` (*scale_exp = 0), else rint(w_i 2^e) with e = fs2_density_scale(wmax,
+ * max(T, 1)).  grid[ny][nx] host; scale_exp, outside nullable.
+ * grid sum + *outside == sum_i q_i cnt_i <= T 2^B <= 2^62 (B of fs2_density_scale); a page
+ * with a referent holds at least one live landmark, so the sum of its referents' amounts
+ * is no more than that total either: no counter of the readout can wrap.
+ * Argument errors and weight validation exactly as fs2_pose_density (bad weights with
+ * `weighted`: FS2_ERR_STATE, nothing written). */
+int fs2_map_density(fs2_handle *h, int32_t weighted, double x0, double y0, double cell,
+                    int32_t nx, int32_t ny, uint64_t *grid, int32_t *scale_exp, uint64_t *outside);
+
+/* Measurement hook (scripts/map_probe.py): as fs2_debug_posterior_times for the two entry
+ * points above; ms: the weight pass with the counts of cnt, the tally, then the summary
+ * pass (fs2_map_summary) or zeroing the grid and the bin pass (fs2_map_density). */
+int fs2_debug_map_times(int32_t enable, double ms[3]);
+
 /* Test hooks of the device generator that replaces the reference's
  * np.random draws when rng="device" (fast_slam_2.py:79,81 motion noise, :183
  * resample start): Philox4x32-10 (Salmon et al., Random123) and the motion

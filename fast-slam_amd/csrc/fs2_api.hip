@@ -33,6 +33,7 @@
 #include "fs2_posterior.hpp"
 #include "fs2_repr.hpp"
 #include "fs2_snapshot.hpp"
+#include "fs2_subsample.hpp"
 
 using namespace fs2;
 static_assert(kMaxRanks <= fs2comm::kShmMaxRanks, "shm transport rank table");
@@ -659,6 +660,11 @@ struct fs2_handle {
     double *map_part = nullptr;
     unsigned long long *map_grid = nullptr;
     size_t map_scr_cap = 0, map_out_cap = 0, map_part_cap = 0, map_grid_cap = 0;
+    // the weighted subsample (fs2_subsample): the scan's words (sized from n) and the
+    // outputs' device copies (sized from the largest k so far), kept between calls
+    unsigned long long *sub_scan = nullptr;
+    char *sub_out = nullptr;
+    size_t sub_scan_cap = 0, sub_out_cap = 0;
 
     MapRef map() const {
         return MapRef{pages.data, pt[cur], std::max<int64_t>(n, 1), rows, records.data, frame, slb, row_boxes(cur),
@@ -1729,6 +1735,7 @@ static void free_handle(fs2_handle *h) {
     hipFree(h->json_text); hipFree(h->json_boff);
     hipFree(h->post_part); hipFree(h->post_out); hipFree(h->post_grid);
     hipFree(h->map_scr); hipFree(h->map_out); hipFree(h->map_part); hipFree(h->map_grid);
+    hipFree(h->sub_scan); hipFree(h->sub_out);
     if (h->post_host) hipHostFree(h->post_host);
     hipFree(h->plan);
     if (h->pub_stats) hipHostFree(h->pub_stats);
@@ -5094,5 +5101,102 @@ int fs2_map_density(fs2_handle *h, int32_t weighted, double x0, double y0, doubl
 }
 
 int fs2_debug_map_times(int32_t enable, double ms[3]) { return g_map_times.debug(enable, ms); }
+
+}  // extern "C"
+
+// ------------------------------------------------ weighted subsample (fs2_subsample.hip) ---
+// k particle indices drawn by weight and the drawn particles' scalars, from the current
+// buffer set.  Only x / y / yaw / w / cnt[cur] are read; what is written is the handle's
+// subsample scratch.
+
+namespace {
+
+// the subsample's three stages (fs2_debug_subsample_times)
+StageTimes<3> g_sub_times;
+struct SubTimer : StageTimer<3> {
+    explicit SubTimer(hipStream_t st) : StageTimer<3>(st, g_sub_times) {}
+};
+
+}  // namespace
+
+extern "C" {
+
+int fs2_subsample(fs2_handle *h, int32_t weighted, int64_t k, uint32_t offset, int64_t *idx, double *x, double *y,
+                  double *yaw, double *w, int32_t *cnt, int32_t *scale_exp, uint64_t *total) {
+    if (!h) return set_err(nullptr, FS2_ERR_ARG, "null handle");
+    if (k < 1 || k > kSubMaxK || !idx)
+        return set_err(&h->err, FS2_ERR_ARG, "fs2_subsample: bad arguments (1 <= k <= 2^30, an idx array)");
+    if (const int rc = post_begin(h, "fs2_subsample")) return rc;
+    const int c = h->cur;
+    const int64_t n = h->n;
+    int32_t e = 0;
+    uint64_t Q = (uint64_t)n;
+    SubScan sc{nullptr, nullptr, nullptr};
+    SubTimer tm(h->stream);
+    if (weighted) {
+        HIP_TRY(h, handle_grow(h, (void **)&h->sub_scan, &h->sub_scan_cap, sizeof(uint64_t) * sub_scan_words(n),
+                               "sub_scan"));
+        double o[kPwRows];
+        tm.mark(0);
+        HIP_TRY(h, launch_weight_scan(h->w[c], n, h->post_part, h->post_out, h->stream));
+        HIP_TRY(h, copy_sync(h, o, h->post_out, sizeof o, hipMemcpyDeviceToHost));
+        if (o[kPwBad] != 0.0 || !density_scale(o[kPwWmax], n, &e))
+            return post_bad_weights(h, "fs2_subsample", o[kPwBad], o[kPwBad] != 0.0 ? 0.0 : o[kPwWmax]);
+        sc = sub_scan_views(h->sub_scan, n);
+        HIP_TRY(h, launch_sub_scan(h->w[c], n, e, sc, h->stream));
+        tm.mark(1);
+    }
+    // the outputs' device copies: idx, then each requested array; the buffer only ever
+    // grows, so a smaller k after a larger one uses its front
+    const size_t b8 = al16((size_t)k * 8), b4 = al16((size_t)k * 4);
+    const size_t need = b8 * (size_t)(1 + (x != nullptr) + (y != nullptr) + (yaw != nullptr) + (w != nullptr)) +
+                        (cnt ? b4 : 0);
+    if (need > h->sub_out_cap)
+        HIP_TRY(h, handle_grow(h, (void **)&h->sub_out, &h->sub_out_cap, need, "sub_out"));
+    char *at = h->sub_out;
+    auto take = [&at](bool wanted, size_t bytes) {
+        char *p = wanted ? at : nullptr;
+        if (wanted) at += bytes;
+        return p;
+    };
+    int64_t *didx = reinterpret_cast<int64_t *>(take(true, b8));
+    SubGather g{};
+    g.x = reinterpret_cast<double *>(take(x != nullptr, b8));
+    g.y = reinterpret_cast<double *>(take(y != nullptr, b8));
+    g.yaw = reinterpret_cast<double *>(take(yaw != nullptr, b8));
+    g.w = reinterpret_cast<double *>(take(w != nullptr, b8));
+    g.cnt = reinterpret_cast<int32_t *>(take(cnt != nullptr, b4));
+    tm.mark(2);
+    HIP_TRY(h, launch_sub_select(sc, n, Q, k, offset, didx, h->stream));
+    tm.mark(3);
+    const bool gather = x || y || yaw || w || cnt;
+    if (gather) {
+        tm.mark(4);
+        HIP_TRY(h, launch_sub_gather(h->x[c], h->y[c], h->yaw[c], h->w[c], h->cnt[c], didx, k, g, h->stream));
+        tm.mark(5);
+    }
+    // every check has passed: from here on the outputs are written
+    if (weighted)
+        HIP_TRY(h, hipMemcpyAsync(&Q, sc.base + post_blocks(n), sizeof Q, hipMemcpyDeviceToHost, h->stream));
+    const std::pair<void *, const void *> f64s[] = {{x, g.x}, {y, g.y}, {yaw, g.yaw}, {w, g.w}};
+    for (const auto &p : f64s)
+        if (p.first) HIP_TRY(h, hipMemcpyAsync(p.first, p.second, (size_t)k * 8, hipMemcpyDeviceToHost, h->stream));
+    if (cnt) HIP_TRY(h, hipMemcpyAsync(cnt, g.cnt, (size_t)k * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, copy_sync(h, idx, didx, (size_t)k * 8, hipMemcpyDeviceToHost));
+    tm.done();
+    if (scale_exp) *scale_exp = e;
+    if (total) *total = Q;
+    return FS2_OK;
+}
+
+int fs2_subsample_threshold(uint64_t total, int64_t k, uint32_t offset, int64_t j, uint64_t *t) {
+    if (!t || total < 1 || total > kSubMaxTotal || k < 1 || k > kSubMaxK || j < 0 || j >= k)
+        return set_err(nullptr, FS2_ERR_ARG,
+                       "fs2_subsample_threshold: bad arguments (1 <= total <= 2^62, 1 <= k <= 2^30, 0 <= j < k, t)");
+    *t = sub_threshold(total, (uint64_t)k, offset, (uint64_t)j);
+    return FS2_OK;
+}
+
+int fs2_debug_subsample_times(int32_t enable, double ms[3]) { return g_sub_times.debug(enable, ms); }
 
 }  // extern "C"

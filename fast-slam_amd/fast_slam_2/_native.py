@@ -248,6 +248,10 @@ SIGNATURES = [
     ("fs2_map_density", C.c_int, [_H, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, _vp,
                                   C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
     ("fs2_debug_map_times", C.c_int, [C.c_int32, _vp]),
+    ("fs2_subsample", C.c_int, [_H, C.c_int32, C.c_int64, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
+    ("fs2_subsample_threshold", C.c_int, [C.c_uint64, C.c_int64, C.c_uint32, C.c_int64, C.POINTER(C.c_uint64)]),
+    ("fs2_debug_subsample_times", C.c_int, [C.c_int32, _vp]),
     ("fs2_debug_philox", C.c_int, [C.c_int32, C.c_int64, _vp, _vp, _vp]),
     ("fs2_debug_normals", C.c_int, [C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int64, _vp]),
     ("fs2_debug_mt_log", C.c_int, [C.c_int32, _vp, C.c_int64, _vp, _vp, C.c_int32]),

@@ -65,6 +65,18 @@ class MapSummary(NamedTuple):
     bbox: np.ndarray            # (4,): min x, min y, max x, max y of the landmark means
 
 
+class Subsample(NamedTuple):
+    """FastSLAM2.subsample's result (k drawn particles)."""
+    idx: np.ndarray             # (k,) int64, non-decreasing particle indices
+    x: np.ndarray               # (k,) the drawn particles' x, y, yaw, weights ...
+    y: np.ndarray
+    yaw: np.ndarray
+    w: np.ndarray
+    counts: np.ndarray          # ... and landmark counts (int32)
+    scale_exp: int              # e of the amounts q = rint(w 2^e) (0 when not weighted)
+    total: int                  # Q, the sum of the amounts
+
+
 def fit_density_window(bbox, shape, origin=None, cell=None):
     """FastSLAM2.pose_density's window rule (documented there): (origin, cell) for a grid
     of shape (ny, nx) over bbox = (xmin, ymin, xmax, ymax), given neither, or one, of them."""
@@ -566,6 +578,48 @@ class FastSLAM2:
             return counts, int(out.value), (x0, y0), cell, int(e.value)
         return (np.ldexp(counts.astype(np.float64), -e.value), float(np.ldexp(float(out.value), -e.value)),
                 (x0, y0), cell)
+
+    # ------------------------------------------------------- weighted subsample
+    def subsample(self, k: int, offset: int | None = None, weighted: bool = True) -> "Subsample":
+        """k particles drawn in proportion to their weights by the systematic sampler, on
+        the device and in integers (fs2_subsample): `idx` (int64,
+        non-decreasing), the drawn particles' `x`, `y`, `yaw`, `w` and landmark `counts`
+        gathered on the device (x[j] is particle idx[j]'s x bit for bit), and `scale_exp`,
+        `total`: the e and Q of the amounts q_i = rint(w_i 2^e) the draw is exact for.
+        Particle i is drawn floor(k q_i / Q) or ceil(k q_i / Q) times and never when
+        q_i = 0; numpy reproduces idx bit for bit (np.cumsum of q, np.searchsorted of the
+        thresholds floor((j Q + floor(offset Q / 2^32)) / k), side="right").
+
+        offset: the sampler's one uniform as a 32-bit integer, u = offset / 2^32.  None
+        means 2^31, the mid-stratum draw, so the call is deterministic.  np.random is
+        never consumed (the drop-in replays depend on numpy's stream being left alone); for
+        a random draw pass offset=int(rng.integers(2**32)) from a generator of your own.
+
+        weighted=True uses the weights as they stand (they need not sum to 1);
+        weighted=False draws every particle equally (idx[j] = floor((j N + s) / k)) and
+        does not read the weights.  The reference does not reset the weights at a resample
+        (DESIGN.md §2, Q8), so right after a resampling scan the unweighted form is the
+        cloud's own posterior.
+
+        snapshot(select=sub.idx) is the thinned filter of the drawn particles, maps
+        included; `restore` it into a FastSLAM2 of k particles.  FS2Error (FS2_ERR_STATE)
+        for a negative or non-finite weight or no positive weight when weighted, on a
+        sharded handle and while a scan is pending; ValueError for k outside [1, 2^30]."""
+        if not getattr(self, "_h", None):
+            raise nat.FS2Error(nat.FS2_ERR_ARG, "subsample() on a closed FastSLAM2 handle")
+        k = int(k)
+        offset = 1 << 31 if offset is None else int(offset)
+        if not 0 <= offset < 1 << 32:
+            raise ValueError("subsample: offset must be an integer in [0, 2^32)")
+        m = k if 1 <= k <= 1 << 30 else 0            # (the library refuses k before it touches an array)
+        idx = np.empty(m, dtype=np.int64)
+        x, y, yaw, w = (np.empty(m) for _ in range(4))
+        cnt = np.empty(m, dtype=np.int32)
+        e, total = C.c_int32(), C.c_uint64()
+        nat.check(self._lib.fs2_subsample(self._h, 1 if weighted else 0, k, offset, nat.ptr(idx), nat.ptr(x),
+                                          nat.ptr(y), nat.ptr(yaw), nat.ptr(w), nat.ptr(cnt), C.byref(e),
+                                          C.byref(total)), self._h)
+        return Subsample(idx, x, y, yaw, w, cnt, int(e.value), int(total.value))
 
     def cluster_landmarks(self, eps: float = 0.5, min_fraction: float = 0.7):
         """Centres [K][2] of DBSCAN over every particle's landmarks, on the device

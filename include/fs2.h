@@ -569,6 +569,48 @@ int fs2_map_density(fs2_handle *h, int32_t weighted, double x0, double y0, doubl
  * pass (fs2_map_summary) or zeroing the grid and the bin pass (fs2_map_density). */
 int fs2_debug_map_times(int32_t enable, double ms[3]);
 
+/* ------------------------------------------------------- weighted subsample ---- */
+
+/* k particles drawn in proportion to their weights by the systematic (low-variance)
+ * sampler, in integers: exact, independent of launch shape, CU count and earlier calls,
+ * and reproducible with numpy bit for bit.  DESIGN.md §16.
+ * Preconditions, the sharded path and the weights' validation exactly as the posterior
+ * readout above (a pending scan, a sharded handle, or -- with `weighted` -- a negative or
+ * non-finite weight or a largest weight that is not positive and finite: FS2_ERR_STATE).
+ * The call changes no filter state, pool, page table, box or free list.
+ *
+ * Amounts: with `weighted`, q_i = rint(w_i 2^e), round half to even, e =
+ * fs2_density_scale(wmax, n) (fs2_pose_density's amounts: q_i <= 2^B, Q = sum q_i <=
+ * 2^62); without it q_i = 1, Q = n, e = 0 and the weights are not read.
+ * Thresholds: C_i = q_0 + ... + q_i; offset stands for the sampler's one uniform
+ * u = offset / 2^32 in [0, 1); s = floor(offset Q / 2^32); for j = 0 .. k - 1
+ *     t_j = floor((j Q + s) / k),   0 <= t_j < Q.
+ * Output: idx[j] = the smallest i with C_i > t_j.  idx is non-decreasing, a particle with
+ * q_i = 0 is never drawn, and particle i is drawn floor(k q_i / Q) or ceil(k q_i / Q)
+ * times.  All of it is 64-bit integer arithmetic: with Q = a k + b and s = a_s k + b_s,
+ *     s = offset (Q >> 32) + ((offset (Q & 0xffffffff)) >> 32),
+ *     t_j = j a + a_s + floor((j b + b_s) / k),   j b + b_s < k^2 <= 2^60.
+ *
+ * idx: host, [k], required.  x, y, yaw, w, cnt: host, [k] each, any may be NULL: the drawn
+ * particles' values gathered on the device, x[j] = x_{idx[j]} bit for bit (fs2_poses_json
+ * formats such pose arrays; fs2_snapshot_save_select(idx) is the thinned filter).
+ * scale_exp, total (nullable): e and Q.
+ * FS2_ERR_ARG: k outside [1, 2^30], idx NULL.  On any error no output is written. */
+int fs2_subsample(fs2_handle *h, int32_t weighted, int64_t k, uint32_t offset, int64_t *idx,
+                  double *x, double *y, double *yaw, double *w, int32_t *cnt, int32_t *scale_exp,
+                  uint64_t *total);
+
+/* t_j of fs2_subsample on the host (no device needed): the same function the kernel
+ * calls.  FS2_ERR_ARG: total outside [1, 2^62], k outside [1, 2^30], j outside [0, k),
+ * t NULL. */
+int fs2_subsample_threshold(uint64_t total, int64_t k, uint32_t offset, int64_t j, uint64_t *t);
+
+/* Measurement hook (scripts/subsample_probe.py): as fs2_debug_posterior_times for
+ * fs2_subsample; ms: the scan (with `weighted`: the weight pass, the read-back of the
+ * largest weight and the three kernels of the prefix sum; else 0), the select, the gather
+ * (0 when no value array is asked for). */
+int fs2_debug_subsample_times(int32_t enable, double ms[3]);
+
 /* Test hooks of the device generator that replaces the reference's
  * np.random draws when rng="device" (fast_slam_2.py:79,81 motion noise, :183
  * resample start): Philox4x32-10 (Salmon et al., Random123) and the motion
